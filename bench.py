@@ -2,7 +2,16 @@
 """Benchmark: steady-state forward Operator throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5]
-                    [--scaling weak|strong] [--no-cpu-baseline] [--no-strong-legs]
+                    [--scaling weak|strong] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-strong-legs]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, the workload and the peak resident memory).  With
+``--dump-outputs DIR`` it also writes what the last timed step returned as DIR/<name>.npy
+(rank 0; the inputs are seeded, so two builds run with the same arguments can be compared output
+for output).  Everything below that takes runs of its own (the kernel's roofline, the adjoint,
+cold and host-tensor legs, the final all-gather, the strong-scaled legs of the default run and
+their one-GPU checks, the CPU baselines) is measured only with ``--full``.
 
 Workload (default, BASELINE configs[1] = SURVEY §8(d) C2): a (50,50,50) SphericalGrid seen by a
 circular orbit of 50 ConeRectGeom((50,100), fov=(45,45)) views, 250,000 rays, float32 density.
@@ -16,9 +25,10 @@ Strong scaling (BASELINE configs[3] and [4] as defined): ``--scaling strong --co
 ONE 50-view / 50-slice dynamic volume over the ranks (each rank its own time slices; a step is
 its forward + dynamic gradient), ``--config c5`` times the static_retrieval.py gd loop with the
 64 views sharded (one gradient all_reduce per iteration; a step is one iteration).  The default
-C2 run reports both legs too (``strong``), each checked against one GPU over the whole orbit.
+C2 run with --full reports both legs too (``strong``), each checked against one GPU over the
+whole orbit.
 
-One JSON line on rank 0: value = rays/s over all ranks; roofline of the forward kernel
+One JSON line on rank 0: value = rays/s over all ranks; with --full, roofline of the forward kernel
 (algorithmic bytes per launch, and the bytes it must stream, over its mean duration back to back
 in a HIP graph between HIP events — what the committed rocprofv3 trace's graph leg reports; the
 dispatch-bound HIP events and the timed steps' span / K beside it); cpu_baseline = the reference's forward (torch CPU on the reference's padded trace,
@@ -191,6 +201,35 @@ def cpu_baseline(cfg, sample_views, reps):
             'host_cpus': os.cpu_count()}
 
 
+DUMP_LIMIT = 60 << 20      # bytes of array data per --dump-outputs directory (under 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each of `arrays` (name -> tensor or sequence of floats) as
+    path/<name>.npy, float64 kept, everything else as float32.  Where all of them together exceed
+    DUMP_LIMIT, an array above its equal share is written as a fixed sample of its flattened
+    elements (sorted indices drawn with torch.Generator().manual_seed(0): the same elements in
+    every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        if not torch.is_tensor(a):
+            a = torch.tensor([float(v) for v in a], dtype=torch.float64)
+        a = a.detach().cpu()
+        host[name] = a if a.dtype == torch.float64 else a.float()
+    share = DUMP_LIMIT // max(len(host), 1)
+    over = sum(a.numel() * a.element_size() for a in host.values()) > DUMP_LIMIT
+    for name, a in host.items():
+        keep = share // a.element_size()
+        if over and a.numel() > keep:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(a.numel(), (keep,), generator=g).sort().values
+            log(f'--dump-outputs: {name} {tuple(a.shape)} written as a sample of {keep} elements')
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a.contiguous().numpy())
+
+
 def _rel(a, b):
     a, b = a.double(), b.double()
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-300))
@@ -227,11 +266,13 @@ class _Ranks:
             torch.cuda.synchronize(self.dev)
 
     def timed(self, fn, reps):
-        """Run fn() `reps` times between barrier + sync brackets -> max seconds over ranks."""
+        """Run fn() `reps` times between barrier + sync brackets -> max seconds over ranks.  What
+        the last call returned is kept in `self.last` (for --dump-outputs)."""
         self.barrier()
         t0 = time.perf_counter()
-        for _ in range(reps):
+        for _ in range(reps - 1):
             fn()
+        self.last = fn()
         self.close()
         return self.max_over_ranks([time.perf_counter() - t0])[0]
 
@@ -281,6 +322,7 @@ def strong_c4(rk, steps, warmup, check=True):
     for _ in range(max(warmup, 2)):     # (the first adjoint builds the time-paired transpose)
         grad = step()
     dt = rk.timed(step, steps)
+    last = {'grad': rk.last}    # this rank's slices of the gradient, from the last timed step
     t_op, = rk.max_over_ranks([t_op])
     out = {'workload': 'C4 strong: ONE dynamic (50,50,50,50) volume, 50-view ConeCirc (100,50) '
                        'orbit, view i <-> time i; views/slices sharded over the ranks',
@@ -313,6 +355,7 @@ def strong_c4(rk, steps, warmup, check=True):
                                    out['grad_rel_diff_vs_1gpu'] <= 1e-5)
         del single
     out['_op'], out['_x'] = op, (x[lo:hi] if sop is not None else x)
+    out['_last'] = last
     del y0
     return out
 
@@ -396,6 +439,8 @@ def strong_c5(rk, iterations, check=True):
                                    out['sqloss_max_rel_diff_vs_1gpu'] <= 1e-9)
         del single
     out['_op'], out['_x'] = op, truth
+    # what the timed gd call returned: coefficients, image stack (gathered), fidelity per iteration
+    out['_last'] = {'coeffs': coeffs, 'stack': stack, 'fidelity': fid}
     return out
 
 
@@ -517,8 +562,8 @@ def roofline(op, x, config, k_ms, k_method):
 
 
 def strong_legs(rk, steps, warmup):
-    """The strong-scaled C4 and C5 legs the default run reports beside its headline, so that
-    every `bench.py --gpus N` run (the driver's N = 1, 2, 4, 8 scaling runs included) also
+    """The strong-scaled C4 and C5 legs the default run reports beside its headline with --full,
+    so that a `bench.py --gpus N --full` run (N = 1, 2, 4, 8) also
     records BASELINE configs[3] and configs[4] as they are defined.  A leg that raises is
     reported as its error (identically on every rank: the legs issue the same collectives)."""
     legs = {}
@@ -540,15 +585,15 @@ def strong_main(args, rk):
     cfg = CONFIGS[args.config]
     torch.cuda.reset_peak_memory_stats(rk.dev)
     if args.config == 'c4':
-        leg = strong_c4(rk, args.steps, args.warmup)
+        leg = strong_c4(rk, args.steps, args.warmup, check=args.full)
         ms, dtype = leg['ms_per_step'], torch.float32
     else:
-        leg = strong_c5(rk, args.steps)
+        leg = strong_c5(rk, args.steps, check=args.full)
         ms, dtype = leg['ms_per_iteration'], torch.float64
     peak_gb = torch.cuda.max_memory_allocated(rk.dev) / 1e9
     op, x = leg['_op'], leg['_x']
-    k_ms, k_method = kernel_time_ms(op, x, reps=50)
-    k_disp, k_med = kernel_dispatch_ms(op, x, reps=max(args.steps, 50))
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(args.dump_outputs, leg['_last'])
     rec = {
         'metric': METRIC,
         'value': leg['rays_per_s'],
@@ -569,8 +614,15 @@ def strong_main(args, rk):
                    'parallelism': f'obs/time-sharded x{rk.world} (strong)'},
         'peak_gb_resident': peak_gb,
         'strong': _public(leg),
-        'roofline': roofline(op, x, args.config, k_ms, k_method),
+        'full': args.full,
     }
+    if not args.full:
+        if rk.rank == 0:
+            print(json.dumps(rec), flush=True)
+        return
+    k_ms, k_method = kernel_time_ms(op, x, reps=50)
+    k_disp, k_med = kernel_dispatch_ms(op, x, reps=max(args.steps, 50))
+    rec['roofline'] = roofline(op, x, args.config, k_ms, k_method)
     rec['roofline']['kernel_ms_dispatch_events'] = k_disp
     rec['roofline']['kernel_ms_dispatch_events_median'] = k_med
     rec['roofline']['scope'] = 'this rank\'s local forward kernel'
@@ -639,7 +691,16 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--config', default='c2', choices=sorted(CONFIGS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline figure: the '
+                         'kernel\'s roofline, the adjoint, cold and host-tensor legs, the final '
+                         'all-gather, the strong-scaled C4 / C5 legs with their one-GPU checks, '
+                         'the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them returned as '
+                         'DIR/<name>.npy (rank 0\'s arrays; float32 or float64, at most 64 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the CPU baselines')
     ap.add_argument('--cpu-sample-views', type=int, default=10)
     ap.add_argument('--cpu-reps', type=int, default=10)
     ap.add_argument('--cpu-cold-views', type=int, default=None,
@@ -650,9 +711,11 @@ def main():
                          'gradient per step; c5: the static_retrieval.py gd loop, one step = one '
                          'iteration)')
     ap.add_argument('--no-strong-legs', action='store_true',
-                    help='skip the strong-scaled C4 / C5 legs the default run reports beside '
-                         'the headline')
+                    help='with --full: skip the strong-scaled C4 / C5 legs the default run reports '
+                         'beside the headline')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.scaling == 'strong' and args.config not in ('c4', 'c5'):
         ap.error('--scaling strong is defined for --config c4 and c5')
 
@@ -725,18 +788,60 @@ def main():
     barrier()
     ev0.record()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    y = step()      # the last timed step's image stack, kept for --dump-outputs
     ev1.record()
     rk.close()
     dt = time.perf_counter() - t0
     k_ms_timed = ev0.elapsed_time(ev1) / args.steps
+    if dist is not None:
+        dt, t_cold = max_over_ranks([dt, t_cold])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'y': y})
+    rec = {
+        'metric': METRIC,
+        'value': n_rays * world * args.steps / dt,
+        'unit': 'rays/s',
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': dt / args.steps * 1e3,
+        'higher_is_better': True,
+        'scaling': 'weak',
+        'vs_baseline': None,
+        'dtype': 'f32' if dtype == torch.float32 else 'f64',
+        'data': 'synthetic (torch.rand density, reference geometry)',
+        'config': {'workload': desc, 'grid': list(shape), 'views_per_gpu': n_views,
+                   'detector': list(det), 'rays_per_gpu': n_rays, 'segments_per_gpu': total_seg,
+                   'parallelism': f'obs-sharded x{world}' + (' (final stack: one RCCL all-gather)' if world > 1 else '')},
+        'peak_gb_resident': torch.cuda.max_memory_allocated(dev) / 1e9,
+        'full': args.full,
+    }
+    if args.full:
+        rec.update(full_weak(args, rk, cfg, grid, op, sop, x, t_cold, k_ms_timed))
+    else:
+        log('legs ' + json.dumps([['first', 1], ['warmup', args.warmup], ['steps', args.steps]]))
+    if rank == 0:
+        print(json.dumps(rec), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_weak(args, rk, cfg, grid, op, sop, x, t_cold, k_ms_timed):
+    """--full: everything a weak-scaled run reports beside its headline, each measured in runs of
+    its own after the timed steps -> the record's further entries (`peak_gb_resident` again, now
+    with these legs' allocations)."""
+    from sph_raytracer_amd import Operator
+    dist, dev, world, rank = rk.dist, rk.dev, rk.world, rk.rank
+    barrier, max_over_ranks = rk.barrier, rk.max_over_ranks
+    shape, n_views, det, kind, dtype, desc = cfg
+    n_rays, total_seg = op._csr['n'], op._csr['total']
     # the forward kernel's own duration over K more launches, each dispatch bracketed by its HIP
     # event pair
     k_ms_disp, k_med_disp = kernel_dispatch_ms(op, x, args.steps)
     gather = None
     if dist is not None:
-        dt, t_cold = max_over_ranks([dt, t_cold])
         # the final image stack: one RCCL all-gather over xGMI, after the loop (north_star), timed
         # on its own; the gathered stack is checked against this rank's own shard
         y_loc = op(x)
@@ -854,21 +959,6 @@ def main():
     roof['frac_timed_span'] = roof['bytes_per_launch'] / (k_ms_timed * 1e-3) / 1e9 / HBM_PEAK_GBS
 
     rec = {
-        'metric': METRIC,
-        'value': n_rays * world * args.steps / dt,
-        'unit': 'rays/s',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': dt / args.steps * 1e3,
-        'higher_is_better': True,
-        'scaling': 'weak',
-        'vs_baseline': None,
-        'dtype': 'f32' if dtype == torch.float32 else 'f64',
-        'data': 'synthetic (torch.rand density, reference geometry)',
-        'config': {'workload': desc, 'grid': list(shape), 'views_per_gpu': n_views,
-                   'detector': list(det), 'rays_per_gpu': n_rays, 'segments_per_gpu': total_seg,
-                   'parallelism': f'obs-sharded x{world}' + (' (final stack: one RCCL all-gather)' if world > 1 else '')},
         'peak_gb_resident': peak_gb,
         'final_gather': gather,
         'adjoint': adjoint,
@@ -898,10 +988,7 @@ def main():
             rec['cpu_baseline']['cold'] = {'value': None, 'error': repr(exc)}
     else:
         rec['cpu_baseline'] = None
-    if rank == 0:
-        print(json.dumps(rec), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    return rec
 
 
 if __name__ == '__main__':

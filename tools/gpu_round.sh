@@ -23,12 +23,12 @@ if [[ $STEPS == *pmc* ]]; then
   done
 fi
 if [[ $STEPS == *bench* ]]; then
-  timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   cat $OUT/bench.json
 fi
 if [[ $STEPS == *prof* ]]; then
   rm -rf $OUT/prof
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --no-cpu-baseline --no-strong-legs > $OUT/prof_bench.json 2> $OUT/prof.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --full --no-cpu-baseline --no-strong-legs > $OUT/prof_bench.json 2> $OUT/prof.err
   for f in $(find $OUT/prof -name "*kernel_stats.csv"); do head -6 "$f"; cp "$f" $OUT/${TAG}_bench_c2_kernel_stats.csv; done
   python tools/rocprof_legs.py $OUT/prof $OUT/prof.err > $OUT/${TAG}_bench_c2_rocprof_legs.json
   cat $OUT/${TAG}_bench_c2_rocprof_legs.json
@@ -36,7 +36,7 @@ fi
 if [[ $STEPS == *configs* ]]; then
   for c in c3 c4 c5; do
     v=10; [ $c = c3 ] && v=4
-    timeout -k 10 300 python bench.py --config $c --steps 50 --warmup 5 --cpu-sample-views $v --cpu-reps 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+    timeout -k 10 300 python bench.py --full --config $c --steps 50 --warmup 5 --cpu-sample-views $v --cpu-reps 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
     cut -c1-200 $OUT/bench_$c.json
   done
 fi

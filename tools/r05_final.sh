@@ -11,8 +11,8 @@ tail -1 $O/r05_gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/r05_smoke.log 2>&1
 tail -1 $O/r05_smoke.log
 timeout -k 10 300 python tools/retrieval_bench.py --out $O/r05_retrieval_c5.json > $O/retrieval.log 2>&1
-timeout -k 10 300 python bench.py > $O/r05_bench_c2.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/r05_bench_c2.json 2> $O/bench.err
 cut -c1-200 $O/r05_bench_c2.json
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/r05_bench_c2_driver_steps20.json 2> $O/bench20.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/r05_bench_c2_driver_steps20.json 2> $O/bench20.err
 cut -c1-200 $O/r05_bench_c2_driver_steps20.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --no-cpu-baseline --no-strong-legs > $O/prof_bench.json 2> $O/prof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --full --no-cpu-baseline --no-strong-legs > $O/prof_bench.json 2> $O/prof.err

@@ -23,8 +23,8 @@ for c in c2 c3 c4 c5; do
 done
 cat $O/r05_operator_times.jsonl
 for c in c4 c5; do
-  SPHRT_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --gpus 2 --config $c --scaling strong --steps 20 --warmup 3 --no-cpu-baseline > $O/r05_strong_${c}_2rank_rehearsal.json 2> $O/strong_$c.err
+  SPHRT_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --full --gpus 2 --config $c --scaling strong --steps 20 --warmup 3 --no-cpu-baseline > $O/r05_strong_${c}_2rank_rehearsal.json 2> $O/strong_$c.err
   cut -c1-300 $O/r05_strong_${c}_2rank_rehearsal.json
-  timeout -k 10 300 python bench.py --config $c --scaling strong --steps 20 --warmup 3 > $O/r05_strong_${c}_1gpu.json 2> $O/strong1_$c.err
+  timeout -k 10 300 python bench.py --full --config $c --scaling strong --steps 20 --warmup 3 > $O/r05_strong_${c}_1gpu.json 2> $O/strong1_$c.err
   cut -c1-300 $O/r05_strong_${c}_1gpu.json
 done

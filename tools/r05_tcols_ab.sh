@@ -9,7 +9,7 @@ O=gpurun_out/tcols; mkdir -p $O; rm -f $O/*.jsonl
 for i in 1 2; do
   for m in trace geom; do
     for c in c2 c3 c5; do
-      SPHRT_TCOLS=$m timeout -k 10 300 python bench.py --config $c --steps 100 --warmup 10 --no-cpu-baseline --no-strong-legs > $O/b.json 2>/dev/null
+      SPHRT_TCOLS=$m timeout -k 10 300 python bench.py --full --config $c --steps 100 --warmup 10 --no-cpu-baseline --no-strong-legs > $O/b.json 2>/dev/null
       python -c "import json;r=json.loads(open('$O/b.json').read().splitlines()[-1]);print(json.dumps({'tcols':'$m','config':'$c','adjoint_us':r['adjoint']['ms_per_step']*1e3,'forward_us':r['ms_per_step']*1e3}))" >> $O/bench.jsonl
     done
     SPHRT_TCOLS=$m timeout -k 10 300 python tools/retrieval_bench.py --out $O/retr.json > /dev/null 2>&1

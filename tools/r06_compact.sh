@@ -9,5 +9,5 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_properties.py tests/test_gp
 tail -1 $O/compact_tests.log
 timeout -k 10 120 python tools/adjoint_stats.py --config c4 > $O/adjstats_c4_compact.json 2> $O/adjstats3.err
 cat $O/adjstats_c4_compact.json
-timeout -k 10 300 python bench.py --config c4 --no-cpu-baseline > $O/bench_c4_compact.json 2> /dev/null
+timeout -k 10 300 python bench.py --full --config c4 --no-cpu-baseline > $O/bench_c4_compact.json 2> /dev/null
 cut -c1-300 $O/bench_c4_compact.json

@@ -10,8 +10,8 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -1 $O/${T}_gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.log 2>&1
 tail -1 $O/${T}_smoke.log
-timeout -k 10 300 python bench.py > $O/${T}_bench_c2_confirm.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/${T}_bench_c2_confirm.json 2> $O/bench.err
 cut -c1-200 $O/${T}_bench_c2_confirm.json
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/${T}_bench_c2_driver_steps20_confirm.json 2> $O/bench20.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/${T}_bench_c2_driver_steps20_confirm.json 2> $O/bench20.err
 cut -c1-200 $O/${T}_bench_c2_driver_steps20_confirm.json
 echo confirm-done

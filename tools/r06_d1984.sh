@@ -14,5 +14,5 @@ for r in 1 2 3; do
   done
 done
 cat $O/r06_ostage1984_ab.jsonl
-timeout -k 10 300 python bench.py --config c4 --no-cpu-baseline > $O/r06_bench_c4_d1984.json 2> $O/bench_c4_d1984.err
+timeout -k 10 300 python bench.py --full --config c4 --no-cpu-baseline > $O/r06_bench_c4_d1984.json 2> $O/bench_c4_d1984.err
 python -c "import json; d=json.load(open('$O/r06_bench_c4_d1984.json')); print('c4 fwd', d['ms_per_step'], 'adj', d['adjoint']['ms_per_step'], 'ratio', d['adjoint']['ms_per_step']/d['ms_per_step'])"

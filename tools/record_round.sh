@@ -10,7 +10,7 @@ STEPS=tests bash tools/gpu_round.sh $TAG
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 tail -1 $O/smoke.log
 if [ -n "$AB" ]; then bash tools/ab_variants.sh c3 "table|compact" $AB; fi
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
 cut -c1-200 $O/bench_driver.json
 STEPS=bench,prof,configs bash tools/gpu_round.sh $TAG
 for c in c2 c3 c4 c5; do
