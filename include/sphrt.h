@@ -292,7 +292,10 @@ int sphrt_csr_index(const int64_t *row_ptr, int64_t n_rays, int32_t *vox, int32_
 /* The same index for a CSR that will take dense output ranges (order bit 2: rows in output order,
  * one output per row or empty row — the time-paired transposed adjoint): block b owns the rows
  * starting in segments [b*1984, (b+1)*1984), n_blocks = sphrt_csr_blocks_dense(n_segments).  The
- * forward reads a CSR with order bit 2 set by these blocks, so its index must come from here. */
+ * forward reads a CSR with order bit 2 set by these blocks, so its index must come from here.
+ * Its blocks zero their output ranges with 16-byte stores placed by element index: the
+ * forward's `out` must be 16-byte aligned, and sphrt_forward_f32/_f64 refuse any other pointer
+ * for such a CSR before launching anything. */
 int64_t sphrt_csr_blocks_dense(int64_t n_segments);
 int sphrt_csr_index_dense(const int64_t *row_ptr, int64_t n_rays, int32_t *vox, int32_t *row_ray,
                           int32_t *empty_ray, int64_t *blocks, int64_t n_blocks,

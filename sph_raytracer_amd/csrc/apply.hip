@@ -2142,6 +2142,9 @@ static int launch_forward(const sphrt_csr* c, const L* len, const T* density, in
     // (dense output ranges read the blocks of sphrt_csr_index_dense: their count at least)
     if (dense && c->n_blocks != c->n_segments / kDenseSegPerBlock + 1)
         return fail("dense output ranges need the blocks of sphrt_csr_index_dense");
+    // (their workgroups zero their ranges with 16-byte stores placed by element index: zero_range)
+    if (dense && (uintptr_t)out % 16 != 0)
+        return fail("dense output ranges need a 16-byte aligned output");
     const T* td = sm.on ? (const T*)c->stage : density;      // what the table kernel gathers
     const int64_t tcs = sm.on ? c->stage_cols : chan_stride;
     if (div > 0) {

@@ -1030,9 +1030,13 @@ class Operator:
         self._fastc = None  # the same bindings inside the CPython entry (csrc/fastpath.cpp)
         self._fastc_T = None  # the adjoint's steady-state bindings (T), same entry
         self._fastc_A = None  # the time-paired adjoint's (dynamic gradient), same entry
+        self._fastA_for = {}  # (y shape, y dtype) -> the density shape _fastc_A's binding serves
+        self._rdev = None     # where T leaves its result: `device`, a GPU named there resolved
         # 'transpose': deterministic voxel-major adjoint (default; a view <-> time pairing
         # transposes its time-paired CSR); 'atomic': float64 atomics (a cross-check, and the
-        # fallback when T * vol does not fit 32-bit columns)
+        # fallback when T * vol does not fit 32-bit columns).  Read on every adjoint call: the
+        # steady-state bindings (_fastc_T, _fastc_A) serve 'transpose' only and stay bound
+        # while another mode is set
         self.adjoint_mode = 'transpose'
         if _compute:
             self._trace()
@@ -1045,6 +1049,8 @@ class Operator:
         current for every allocation and launch; later calls run there too (_cdev)."""
         dev = _lib.require_gpu(self.device)
         self._cdev = dev
+        # ('cuda' without an index names the compute device, as for the trace)
+        self._rdev = dev if tr.device(self.device).type == 'cuda' else tr.device(self.device)
         with tr.cuda.device(dev):
             self._trace_on(dev)
 
@@ -1624,10 +1630,14 @@ class Operator:
 
     def _apply_adjoint(self, y, dshape, ddtype, ddevice, trace_order=False):
         fa = self._fastc_A
-        if fa is not None and not trace_order and y.dtype == ddtype and ddevice == self._cdev:
+        if fa is not None and self.adjoint_mode == 'transpose' and not trace_order \
+                and y.dtype == ddtype and ddevice == self._cdev \
+                and self._fastA_for.get((y.shape, y.dtype)) == dshape:
             # steady state of the time-paired adjoint in one C call (y gathered into trace
             # order and the transposed forward, csrc/fastpath.cpp): the autograd backward of a
-            # dynamic forward and Operator.T(y, time_slices=True) land here
+            # dynamic forward and Operator.T(y, time_slices=True) land here.  The entry matches
+            # y alone, and a (1, nr, ne, na) density has the same y: only the density shape it
+            # was bound for
             out = self._fastfn(fa, y)
             if out is not None:
                 return out
@@ -1667,6 +1677,7 @@ class Operator:
                  _lib.address(fn), ctypes.addressof(tdesc), 1, csr['n'], 0, tdesc.n_rays,
                  tuple(dshape), _stage_bytes(tdesc, 1, y.element_size()), perm,
                  _lib.address(gfn))
+        self._fastA_for[(y.shape, y.dtype)] = tuple(dshape)
 
     def _tcols_geom(self):
         """Whether the transposed CSRs of a reordered trace (wedges, view tiles) take their
@@ -1763,15 +1774,15 @@ class Operator:
             if self._csr is None:
                 raise RuntimeError('Operator was built with _compute=False')
             dshape = (int(y.shape[0]),) + tuple(int(v) for v in self.grid.shape[1:])
-            return self._apply_adjoint(y, dshape, y.dtype, tr.device(self.device))
+            return self._apply_adjoint(y, dshape, y.dtype, self._rdev)
         fc = self._fastc_T
-        if fc is not None:
+        if fc is not None and self.adjoint_mode == 'transpose':
             # steady state in one C call: the transposed CSR's forward (csrc/fastpath.cpp)
             out = self._fastfn(fc, line_integrations)
             if out is not None:
                 return out
         y = tr.as_tensor(line_integrations)
-        res = self._apply_adjoint(y, tuple(self.grid.shape), y.dtype, tr.device(self.device))
+        res = self._apply_adjoint(y, tuple(self.grid.shape), y.dtype, self._rdev)
         self._bind_adjoint(y, res)
         return res
 

@@ -35,7 +35,22 @@ def c2(gpu):
     return grid, geom, Operator(grid, geom, device=gpu)
 
 
-def test_adjoint_identity_and_determinism(c2, gpu):
+def _count_atomic(monkeypatch):
+    """A counter over the float64-atomic adjoint's entry point (raytracer.py looks it up per
+    call): [launches]."""
+    from sph_raytracer_amd import _lib
+    lib = _lib.load()
+    real, calls = lib.sphrt_adjoint_accumulate, [0]
+
+    def counted(*args):
+        calls[0] += 1
+        return real(*args)
+
+    monkeypatch.setattr(lib, 'sphrt_adjoint_accumulate', counted)
+    return calls
+
+
+def test_adjoint_identity_and_determinism(c2, gpu, monkeypatch):
     grid, geom, op = c2
     g = tr.Generator(device=gpu).manual_seed(0)
     x = tr.rand(grid.shape, dtype=tr.float64, device=gpu, generator=g)
@@ -47,10 +62,16 @@ def test_adjoint_identity_and_determinism(c2, gpu):
     assert tr.equal(op(x), ax), 'forward not bitwise reproducible'
     assert tr.equal(op.T(y), aty), 'adjoint not bitwise reproducible'
     # deterministic transposed adjoint == float64-atomic adjoint (up to summation order)
+    atomic = _count_atomic(monkeypatch)
+    assert op._fastc_T is not None                 # (bound above: the mode must still hold)
     op.adjoint_mode = 'atomic'
-    at2 = op.T(y)
-    op.adjoint_mode = 'transpose'
+    try:
+        at2 = op.T(y)
+    finally:
+        op.adjoint_mode = 'transpose'
+    assert atomic == [1], 'the atomic leg did not run sphrt_adjoint_accumulate'
     assert tr.allclose(at2, aty, rtol=1e-12, atol=1e-12 * float(aty.abs().max()))
+    assert tr.equal(op.T(y), aty) and atomic == [1]
     # float32 forward/adjoint against float64
     ax32 = op(x.float())
     assert float(((ax32.double() - ax).abs() / ax.abs().clamp_min(1e-12)).max()) <= 1e-5
@@ -636,8 +657,18 @@ def test_dynamic_operator_T_time_slices(gpu, dt):
     # the steady-state binding (csrc/fastpath.cpp: gather into trace order + transposed forward)
     # serves the later calls: the same bits
     assert op._fastc_A is not None
-    assert tr.equal(op.T(y, time_slices=True), got)
+    served, fastfn = [], op._fastfn
+
+    def spy(capsule, arg):
+        out = fastfn(capsule, arg)
+        served.append((capsule is op._fastc_A, out is not None))
+        return out
+
+    op._fastfn = spy
+    assert tr.equal(op.T(y, time_slices=True), got) and served == [(True, True)]
     assert tr.equal(op._apply_adjoint(y, tuple(grid.shape), dt, gpu), got)
+    assert served == [(True, True)] * 2
+    op._fastfn = fastfn
     # one geometry seen at every time step: slice t = the static adjoint of image t
     single = geom.geoms[0]
     op1 = Operator(grid, single, device=gpu)
@@ -649,7 +680,7 @@ def test_dynamic_operator_T_time_slices(gpu, dt):
     assert tr.allclose(got1, want, rtol=tol, atol=tol * float(want.abs().max()))
 
 
-def test_dynamic_pairing_forward_and_adjoint(gpu):
+def test_dynamic_pairing_forward_and_adjoint(gpu, monkeypatch):
     """View i <-> time slice i (dynamic grid, a collection of T views): the forward runs on the
     time-paired CSR (granule tables over the flattened (T, vol) density) and the adjoint on its
     transpose.  Forward equals the per-segment time-slice gather of the trace's CSR bitwise in
@@ -677,10 +708,15 @@ def test_dynamic_pairing_forward_and_adjoint(gpu):
     xg = x.clone().requires_grad_(True)
     (op(xg) * y).sum().backward()
     atx = xg.grad
+    atomic = _count_atomic(monkeypatch)
+    assert op._fastc_A is not None                 # (bound above: the mode must still hold)
     op.adjoint_mode = 'atomic'
     xa = x.clone().requires_grad_(True)
-    (op(xa) * y).sum().backward()
-    op.adjoint_mode = 'transpose'
+    try:
+        (op(xa) * y).sum().backward()
+    finally:
+        op.adjoint_mode = 'transpose'
+    assert atomic == [1], 'the atomic leg did not run sphrt_adjoint_accumulate'
     assert tr.allclose(atx, xa.grad, rtol=1e-12, atol=1e-14)
     lhs, rhs = (fx * y).sum().item(), (x * atx).sum().item()
     assert abs(lhs - rhs) <= 1e-12 * abs(lhs)
