@@ -711,7 +711,11 @@ __device__ void trace_one(const GridDev& G, const RayGeo& g, const double t1c_o,
     // entry state is reduced across the wave below; a tie of different values in its last group
     // defers the ray, exactly as a tie inside the list would.  (C2: 85 -> 62 entries per ray.)
     // t1c_o = sqrt(r_outer^2 - dd^2), sphere nr's half chord (from the hit record)
-    const double t_lo = g.tc - t1c_o, t_hi = g.tc + t1c_o;
+    // A start on the outer sphere itself can have its exit behind it by an ulp (t_hi < 0) and a
+    // valid start shell (find_starts): the exit is then never listed, the r row keeps the start
+    // shell, and the reference goes on through every cone / half-plane ahead — no clip at t_hi.
+    const double t_lo = g.tc - t1c_o;
+    const double t_hi = (sr >= 0 && sr < G.nr && g.tc + t1c_o < 0.0) ? kInf : g.tc + t1c_o;
     const bool clip_lo = t_lo > 0.0;
     auto keep = [&](double t) {
         return __builtin_isfinite(t) && !(t < 0.0) && !(t > t_hi) && !(clip_lo && t < t_lo);
@@ -1171,8 +1175,15 @@ __global__ __launch_bounds__(256) void screen_kernel(GridDev G, RaysDev R, Trace
     const bool start_r_ok = s[0] >= 0 && s[0] < G.nr;
     const bool hit = active && !(!start_r_ok && __builtin_isnan(t1c_outer));
     if (MODE == MODE_BOUND && active)
-        o.counts[ray] = hit ? segment_bound(G, g, start_r_ok && s[1] >= 0 && s[1] < G.ne &&
-                                                      s[2] >= 0 && s[2] < G.na, rb, eb, ab)
+        // (a valid start shell whose outer exit is not ahead — at the start itself for a tangent
+        // from the sphere, where the exit ties with the start entry and the exact path may keep
+        // the start's shell; behind the start by an ulp; or NaN for a line through the origin
+        // whose dd^2 rounds below zero: every crossing ahead can be listed, so K like a start
+        // inside a voxel)
+        o.counts[ray] = hit ? segment_bound(G, g, start_r_ok &&
+                                                      ((s[1] >= 0 && s[1] < G.ne && s[2] >= 0 &&
+                                                        s[2] < G.na) || !(g.tc + t1c_outer > 0.0)),
+                                            rb, eb, ab)
                             : 0;
     if (active && !hit) {
         if (MODE == MODE_COUNT) o.counts[ray] = 0;

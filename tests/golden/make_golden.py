@@ -2,6 +2,7 @@
 
     python tests/golden/make_golden.py          # trace / forward / adjoint fixtures
     python tests/golden/make_golden.py pins     # dynamic gradients, multichannel, gd() run
+    python tests/golden/make_golden.py lattice  # the tie lattice: lattice_*, solvers_lattice
 
 Every case stores its INPUTS (grid boundaries, ray starts, ray directions as the reference
 geometry produced them, densities, adjoint inputs) and the reference's OUTPUTS (non-zero trace
@@ -48,7 +49,7 @@ def grid_arrays(grid):
                 shape=np.array(tuple(grid.shape)), dynamic=np.array(grid.dynamic))
 
 
-def save_case(name, grid, geom, densities=(), ys=(), note='', keep_dense=False):
+def save_case(name, grid, geom, densities=(), ys=(), note='', keep_dense=False, extra=None):
     tr.manual_seed(1234)
     xs = geom.ray_starts.clone()
     rays = geom.rays.clone()     # as the reference geometry produced them (before tracing)
@@ -71,6 +72,7 @@ def save_case(name, grid, geom, densities=(), ys=(), note='', keep_dense=False):
     if keep_dense:
         out['dense_regs'] = op.regs.numpy().astype(np.int32)
         out['dense_lens'] = op.lens.numpy()
+    out.update(extra or {})
     path = os.path.join(HERE, f'{name}.npz')
     np.savez_compressed(path, **out)
     print(f'{name}: rays={int(np.prod(op.lens.shape[:-1]))} K={op.lens.shape[-1]} '
@@ -202,7 +204,7 @@ def pins():
     gd_case()
 
 
-def save_api_case(name, grid, geom, densities=(), ys=(), note='', **op_kw):
+def save_api_case(name, grid, geom, densities=(), ys=(), note='', extra=None, **op_kw):
     """An Operator(..., **op_kw) case (ftype=float32, invalid=True): inputs, the reference's dense
     (regs, lens) exactly as it returns them (lens in the trace's ftype, invalid entries kept), its
     forward on float32 and float64 densities and its adjoint T(y)."""
@@ -222,6 +224,7 @@ def save_api_case(name, grid, geom, densities=(), ys=(), note='', **op_kw):
             out[f'adj32_{i}'] = op.T(y.to(tr.float32)).numpy()
         except RuntimeError as exc:
             out[f'adj32_{i}_error'] = np.array(str(exc))
+    out.update(extra or {})
     path = os.path.join(HERE, f'{name}.npz')
     np.savez_compressed(path, **out)
     lens = op.lens
@@ -296,6 +299,108 @@ def api_surface():
               ys=[tr.rand(vg.shape, generator=g, dtype=tr.float64)],
               note='ParallelGeom (30,40) at (5,0.5,1), size 2.2: ViewGeom(ray_starts, rays '
                    'expanded) (SURVEY App. C.2)')
+
+
+def lattice_rays():
+    """7^3 starts with coordinates in {-2, -1, -1/2, 0, 1/2, 1, 2} x the 26 directions with
+    components in {-1, 0, 1}: 8918 rays that tie systematically (through the z axis, the origin,
+    in half-planes and the xy-plane, along +-z; starts on shells, cones, the axis, the origin)."""
+    c = tr.tensor([-2, -1, -0.5, 0, 0.5, 1, 2], dtype=tr.float64)
+    starts = tr.cartesian_prod(c, c, c)
+    u = tr.tensor([-1, 0, 1], dtype=tr.float64)
+    dirs = tr.cartesian_prod(u, u, u)
+    dirs = dirs[dirs.abs().sum(1) > 0]
+    xs = starts[:, None, :].expand(-1, len(dirs), -1).reshape(-1, 3).clone()
+    rays = dirs[None, :, :].expand(len(starts), -1, -1).reshape(-1, 3).clone()
+    return xs, rays
+
+
+def sqrt_sensitive_mask(grid, geom):
+    """Bool per ray: the oracle's canonical voxel sequence (golden_cases.canonical at the
+    contract's tiny) differs between MKL and IEEE square roots.  From the oracle only."""
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    sys.path.insert(0, os.path.join(HERE, '..', '..'))
+    import golden_cases as gc
+    from oracle import oracle
+    xs, rays = geom.ray_starts.numpy().copy(), geom.rays.numpy().copy()
+    starts = RT.find_starts(grid, geom.ray_starts).numpy()
+    g = oracle.Grid.from_boundaries(grid.r_b.numpy(), grid.e_b.numpy(), grid.a_b.numpy())
+    if not oracle.use_mkl_sqrt(True):
+        raise RuntimeError('vdSqrt is not exported by this torch build: no sqrt_sensitive mask')
+    mkl = oracle.trace_segments(g, xs, rays, starts)
+    oracle.use_mkl_sqrt(False)
+    ieee = oracle.trace_segments(g, xs, rays, starts)
+    scale = max(float(grid.r_b.abs().max()), float(np.abs(xs).max()))
+    return gc.sequence_differs(mkl, ieee, gc.TINY * scale)
+
+
+def sqrt_sensitive_dense_mask(grid, geom, f32):
+    """Bool per ray of a reference-mode case: the oracle's dense regs (every entry, the
+    zero-length, NaN and out-of-grid ones included) differ between MKL and IEEE square roots."""
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    sys.path.insert(0, os.path.join(HERE, '..', '..'))
+    import golden_cases as gc
+    from oracle import oracle
+    case = dict(grid_arrays(grid), xs=geom.ray_starts.numpy().copy(), rays=geom.rays.numpy().copy())
+    g = oracle.Grid.from_boundaries(case['r_b'], case['e_b'], case['a_b'],
+                                    ftype='float32' if f32 else 'float64')
+    starts = gc.ref_mode_starts(case, f32)
+    if not oracle.use_mkl_sqrt(True):
+        raise RuntimeError('vdSqrt is not exported by this torch build: no sqrt_sensitive mask')
+    mkl, _ = oracle.trace_dense(g, case['xs'], case['rays'], starts, invalid=not f32)
+    oracle.use_mkl_sqrt(False)
+    ieee, _ = oracle.trace_dense(g, case['xs'], case['rays'], starts, invalid=not f32)
+    return (mkl != ieee).any(axis=(0, -1)).reshape(-1)
+
+
+def lattice():
+    """The tie lattice on four grids (trace / forward / adjoint fixtures with the per-ray
+    sqrt_sensitive mask, y zero on masked rays), in the reference modes, and through the
+    per-family solvers."""
+    g = tr.Generator().manual_seed(77)
+    xs, rays = lattice_rays()
+    grids = dict(
+        lattice_full=G.SphericalGrid(shape=(4, 4, 4)),
+        lattice_a2pi=G.SphericalGrid(shape=(5, 3, 7), size_a=(0, 2 * tr.pi)),
+        lattice_hollow=G.SphericalGrid(shape=(3, 6, 8), size_r=(0.5, 1.5)),
+        # nba > 64: the azimuth wedge.  a in [0, 2 pi]: with [-pi, pi] the voxel behind the z axis
+        # of 5 through-axis rays (e.g. start (-1, -1, -2) along (1, 1, 1)) turns on the last bit
+        # of the host's cos / sin tables (MKL's AVX-512 against its AVX2 / SSE4.2 kernels, checked
+        # with MKL_ENABLE_INSTRUCTIONS); this range gives one trace under all three
+        lattice_wide_a=G.SphericalGrid(shape=(3, 4, 100), size_a=(0, 2 * tr.pi)))
+    for name, grid in grids.items():
+        geom = G.ViewGeom(xs.clone(), rays.clone())
+        mask = sqrt_sensitive_mask(grid, geom)
+        y = tr.rand(geom.shape, generator=g, dtype=tr.float64)
+        y[tr.from_numpy(mask)] = 0
+        save_case(name, grid, geom, densities=[tr.rand(grid.shape, generator=g)], ys=[y],
+                  note=f'tie lattice, grid {tuple(grid.shape)}', extra=dict(sqrt_sensitive=mask))
+        print(f'{name}: sqrt_sensitive {int(mask.sum())} of {len(mask)} rays ({mask.mean():.4f})')
+    grid = G.SphericalGrid(shape=(4, 4, 4))
+    for name, kw in (('lattice_f32', dict(ftype=tr.float32)), ('lattice_invalid', dict(invalid=True))):
+        geom = G.ViewGeom(xs.clone(), rays.clone())
+        mask = sqrt_sensitive_dense_mask(grid, geom, 'ftype' in kw)
+        save_api_case(name, grid, geom, densities=[tr.rand(grid.shape, generator=g)],
+                      ys=[tr.rand(geom.shape, generator=g, dtype=tr.float64)],
+                      note=f'tie lattice, grid (4, 4, 4), {kw}', extra=dict(sqrt_sensitive=mask),
+                      **kw)
+        print(f'{name}: sqrt_sensitive (dense regs) {int(mask.sum())} of {len(mask)} rays')
+    # the per-family solvers on the lattice rays (as solver_case: 5 boundaries per family)
+    geom = G.ViewGeom(xs.clone(), rays.clone())
+    sx, sr = geom.ray_starts, geom.rays
+    r_b = tr.linspace(0, 1, 5, dtype=tr.float64)
+    e_b = tr.linspace(0, tr.pi, 5, dtype=tr.float64)
+    a_b = tr.linspace(-tr.pi, tr.pi, 5, dtype=tr.float64)
+    out = dict(xs=sx.numpy().copy(), rays=sr.numpy().copy(), r_b=r_b.numpy(), e_b=e_b.numpy(),
+               a_b=a_b.numpy())
+    for key, fn, b in (('r', RT.r_torch, r_b), ('e', RT.e_torch, e_b), ('a', RT.a_torch, a_b)):
+        t, reg, _, neg = fn(b, sx.clone(), sr.clone())
+        out[f'{key}_t'] = t.numpy()
+        out[f'{key}_reg'] = reg.numpy().astype(np.int32)
+        out[f'{key}_neg'] = neg.numpy().astype(np.int8)
+    path = os.path.join(HERE, 'solvers_lattice.npz')
+    np.savez_compressed(path, **out)
+    print(f'solvers_lattice: {len(sx)} rays -> {os.path.getsize(path) / 1e3:.0f} kB')
 
 
 def main():
@@ -387,6 +492,8 @@ if __name__ == '__main__':
         pins()
     elif arg == ['api']:
         api_surface()
+    elif arg == ['lattice']:     # lattice_*, solvers_lattice
+        lattice()
     elif arg == ['gd32']:
         gd_case('gd_circ32', n_iter=20, n=32, n_views=32, det=(50, 40))
     else:

@@ -14,6 +14,12 @@ CASES = ['c1_single_vantage', 'c2_orbit3', 'circ_orbit', 'inside_starts', 'parti
          'log_grid', 'dynamic_obs', 'parallel_geom'] + [f'optest_{i}' for i in range(5)]
 F32_CASES = ['f32_rect', 'f32_circ', 'f32_inside']        # Operator(..., ftype=float32)
 INVALID_CASES = ['invalid_rect', 'invalid_inside']        # Operator(..., invalid=True)
+# the tie lattice (make_golden.py lattice): 7^3 dyadic starts x 26 directions on four grids, each
+# with a per-ray `sqrt_sensitive` mask; the same rays in the reference modes and the solvers
+LATTICE_CASES = ['lattice_full', 'lattice_a2pi', 'lattice_hollow', 'lattice_wide_a']
+LATTICE_F32_CASES = ['lattice_f32']
+LATTICE_INVALID_CASES = ['lattice_invalid']
+LATTICE_SOLVERS = 'solvers_lattice'
 
 TINY = 1e-12           # segments shorter than TINY*scale are tie/ulp artefacts
 LEN_RTOL = 1e-12       # lengths, float64
@@ -102,6 +108,31 @@ def compare_segments(ref, got, scale, what='', tiny=TINY, len_rtol=LEN_RTOL, len
         k = int(np.argmax(err - tol))
         return f'{what}: length mismatch {lr[k]!r} vs {lg[k]!r} (|d|={err[k]:.3g})'
     return None
+
+
+def sequence_differs(a, b, tiny):
+    """a, b: (ptr, vox, len) of the same rays.  Bool per ray: True where the canonical voxel
+    sequences (segments under `tiny` dropped, equal neighbours merged) differ."""
+    pa, va, _ = canonical(*a, tiny)
+    pb, vb, _ = canonical(*b, tiny)
+    n = len(pa) - 1
+    assert len(pb) - 1 == n
+    ca, cb = np.diff(pa), np.diff(pb)
+    diff = ca != cb
+    ray_a, ray_b = np.repeat(np.arange(n), ca), np.repeat(np.arange(n), cb)
+    ka, kb = ~diff[ray_a], ~diff[ray_b]
+    diff[np.unique(ray_a[ka][va[ka] != vb[kb]])] = True
+    return diff
+
+
+def take_rays(ptr, vox, seg, keep):
+    """The CSR (ptr, vox, len) restricted to the rays where the bool array `keep` is set."""
+    ptr = np.asarray(ptr, np.int64)
+    keep = np.asarray(keep, bool).reshape(-1)
+    cnt = np.diff(ptr)
+    k = np.repeat(keep, cnt)
+    return (np.concatenate([[0], np.cumsum(cnt[keep])]).astype(np.int64),
+            np.asarray(vox)[k], np.asarray(seg)[k])
 
 
 def dense_to_segments(regs, lens, grid_shape, invalid=False):
