@@ -220,7 +220,7 @@ int sphrt_rays_cone_tiled(int64_t n_views, int64_t h, int64_t w, int circ, const
  * (uint16, n_segments entries) for every block of at most 4096 segments and 2046 granules; with
  * loc/tab/n_cols/tab_stride set, a static forward on a 16-byte-aligned density stages each
  * block's granules in LDS (4 * (tab_stride + 1) elements, up to 64 KB) instead of gathering per
- * segment.
+ * segment; sphrt_forward_plan makes that choice and reports it.
  * Per-segment arrays (vox, len, len32, loc) are read in aligned 8- or 16-entry chunks: allocate
  * them to round_up(n_segments, 16) entries (the entries past n_segments are never used).  `len32` is
  * the float32 copy of `len` used by the float32 forward: sphrt_csr_local_count / _build write it
@@ -229,6 +229,10 @@ int sphrt_rays_cone_tiled(int64_t n_views, int64_t h, int64_t w, int circ, const
 #define SPHRT_ROW_HEAD 0x80000000u
 #define SPHRT_BLOCK_FIELDS 6   /* int64 per entry of blocks */
 #define SPHRT_LOC_HEAD 0x8000u
+/* Forward workgroups resident at once on an MI355X (256 CUs x 6): grids up to this size run as one
+ * wave.  The block order (sphrt_csr.order), the staged build's row search and the Python layer's
+ * brick / alternation rules all switch here. */
+#define SPHRT_SINGLE_WAVE_BLOCKS 1536
 typedef struct sphrt_csr {
     int64_t n_rays;
     int64_t n_segments;
@@ -373,6 +377,32 @@ int sphrt_forward_f32(const sphrt_csr *csr, const float *density, int64_t n_chan
 int sphrt_forward_f64(const sphrt_csr *csr, const double *density, int64_t n_chan,
                       int64_t chan_stride, int64_t ray_chan_div, double *out,
                       int64_t out_chan_stride, void *stream);
+
+/* Which forward_kernel instantiation sphrt_forward_f32/_f64 launch for a call, and how.  The
+ * library decides this in one place and the forwards dispatch from the same record; callers read
+ * it for reports only (the Python layer formats it into the kernel's name).  Flags are 0 / 1. */
+typedef struct sphrt_fwd_plan {
+    int32_t mode;             /* 0: granule tables staged in LDS, 1: per-segment gathers through
+                                 vox, 2: time slices (ray_chan_div > 0)                          */
+    int32_t tab_bytes;        /* width of the table entries read: 2 or 4 (4 when mode != 0)      */
+    int32_t edma;             /* granule DMA issued before the block record (whole-granule cols) */
+    int32_t runs;             /* rows' rays from the run records (sphrt_csr.runs)                */
+    int32_t half;             /* float64 half tables: the LDS image holds half a table at a time */
+    int32_t dense;            /* dense output ranges (sphrt_csr.order bit 2)                     */
+    int32_t early_rounds;     /* 256-entry table chunks fetched early (the kernel's GE argument) */
+    int32_t segs_per_thread;  /* segments per thread per pass (workgroups of 2048 / this)        */
+    int32_t fallback;         /* a second, gather launch follows for the blocks without a table  */
+    int32_t lds_bytes;        /* dynamic LDS per workgroup of the main launch                    */
+    int32_t chunk;            /* block order: consecutive blocks dealt per XCD (0: dispatch
+                                 order, INT32_MAX: one range per XCD; ~chunk: reversed)          */
+    int32_t elem_bytes;       /* 4: float32 density, lengths and output, 8: float64              */
+} sphrt_fwd_plan;
+/* The plan of sphrt_forward_f32 (elem_bytes 4) / _f64 (8) called with these arguments.  Host code
+ * only: no device is touched and no pointer is dereferenced except csr; `density` counts by its
+ * address (granule alignment), and a brick-staged CSR's by its `stage` pointer (NULL: aligned).
+ * Fails as the forward would on arguments it refuses before looking at `out` or the stage. */
+int sphrt_forward_plan(const sphrt_csr *csr, int elem_bytes, const void *density, int64_t n_chan,
+                       int64_t chan_stride, int64_t ray_chan_div, sphrt_fwd_plan *out);
 
 /* Kernel timing for measurement (bench.py's roofline; no reference counterpart): the next
  * sphrt_forward_f32/f64 call on this host thread launches its main forward kernel with these two

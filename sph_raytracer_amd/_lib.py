@@ -45,7 +45,14 @@ class CSR(ctypes.Structure):
                 ('stage_packed', c_i64)]
 
 
+class ForwardPlan(ctypes.Structure):
+    _fields_ = [(name, c_i32) for name in (
+        'mode', 'tab_bytes', 'edma', 'runs', 'half', 'dense', 'early_rounds', 'segs_per_thread',
+        'fallback', 'lds_bytes', 'chunk', 'elem_bytes')]
+
+
 ROW_HEAD = 0x80000000
+SINGLE_WAVE_BLOCKS = 1536  # SPHRT_SINGLE_WAVE_BLOCKS
 BLOCK_FIELDS = 6           # SPHRT_BLOCK_FIELDS
 LOC_HEAD = 0x8000          # SPHRT_LOC_HEAD
 TAB_WIDE = 2048            # SPHRT_TAB_WIDE
@@ -106,6 +113,8 @@ _SIGNATURES = [
                                   c_vp]),
     ('sphrt_forward_f64', c_int, [ctypes.POINTER(CSR), c_vp, c_i64, c_i64, c_i64, c_vp, c_i64,
                                   c_vp]),
+    ('sphrt_forward_plan', c_int, [ctypes.POINTER(CSR), c_int, c_vp, c_i64, c_i64, c_i64,
+                                   ctypes.POINTER(ForwardPlan)]),
     ('sphrt_time_next_forward', c_int, [c_vp, c_vp]),
     ('sphrt_adjoint_accumulate', c_int, [ctypes.POINTER(CSR), c_vp, c_int, c_i64, c_i64, c_i64,
                                          c_vp, c_i64, c_vp]),

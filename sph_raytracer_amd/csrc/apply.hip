@@ -531,7 +531,7 @@ __device__ __forceinline__ void staged_gather(const Staged& S, const int64_t* bl
     // over the row starts per segment (C3 table kernel 1120 -> 1107 us, C5 198 -> 190 us); a
     // one-wave grid (C2) is bound by each workgroup's chain, which the extra barrier lengthens
     // (35 -> 41 us), and keeps the search (profiles/r05_gather_ab.json)
-    const bool rid_ok = nb > 256 * 6 && in_lds &&
+    const bool rid_ok = nb > SPHRT_SINGLE_WAVE_BLOCKS && in_lds &&
                         rs_bytes + (size_t)nrow * 8 + (size_t)n * 2 <= lds_cap;
     uint16_t* rid = reinterpret_cast<uint16_t*>(lds + rs_bytes + (size_t)nrow * 8);
     if (in_lds) {
@@ -2045,38 +2045,20 @@ static int check_csr(const sphrt_csr* c, int64_t n_chan, int64_t div) {
     return 0;
 }
 
-// The granule tables apply to static channels whose granules are 16-byte (float) / 32-byte
-// (double) aligned; anything else takes the per-segment gather through vox.
 // dynamic LDS for the staged granules, per workgroup (C5 f64, 49 KB: table 64.0 us vs per-segment
 // gather 73.3 us)
 constexpr size_t kTableLdsMax = 64 * 1024;
+// float64 tables that leave fewer than 4 workgroups per CU (over 40 KB of LDS): half
+// tables, 5 per CU (C5 forward f64 62.1 -> 53.0 us, transposed adjoint 58.8 -> 53.7 us).
+// Not below: C3's 34.8 KB tables (4 per CU) measured 364 -> 383 us with halves (more
+// resident workgroups, more L2 misses; few of its tables even need the second phase).
+constexpr size_t kHalfTabMinLds = 40 * 1024;
 
-// Early granule DMA (forward_kernel EDMA) needs whole granules only: no partial last granule.
 // SPHRT_FWD_HALF=0 in the environment at launch keeps whole float64 tables (tests: half tables
 // give the whole tables' sums bit for bit).
 static bool half_tables_on() {
     const char* e = getenv("SPHRT_FWD_HALF");
     return !(e && e[0] == '0');
-}
-
-static bool early_dma(const sphrt_csr* c) {
-    return table_cols(c) % 4 == 0 &&
-           (size_t)(kGranEarly * kThreads + 1) * 4 * 8 <= kTableLdsMax;
-}
-
-template <typename T>
-static bool use_tables(const sphrt_csr* c, const T* density, int64_t n_chan, int64_t chan_stride,
-                       int64_t div) {
-    if (!c->loc || !c->tab || c->n_cols <= 0 || div > 0) return false;
-    // (+ the staged output range of dense output ranges, which the granule image leaves room for)
-    const size_t extra = (c->order & 4) ? (size_t)kOutStage * sizeof(T) : 0;
-    if (c->tab_stride < 1 ||
-        (size_t)(imax64(c->tab_stride, kGranEarly * kThreads) + 1) * 4 * sizeof(T) + extra >
-            kTableLdsMax)
-        return false;
-    if ((uintptr_t)density % (4 * sizeof(T)) != 0) return false;
-    if (n_chan > 1 && chan_stride % 4 != 0) return false;
-    return true;
 }
 
 // Workgroup order of a forward launch (block_of).  Measured on MI355X (profiles/r01_apply_kernels):
@@ -2095,7 +2077,7 @@ static int fwd_chunk(const sphrt_csr* c, size_t elem) {
     const int64_t bytes = c->n_cols * (int64_t)elem;
     int k = (c->order & 2) ? INT32_MAX
             : bytes > (int64_t)(4 << 20) ? 64
-            : c->n_blocks <= 256 * 6 ? INT32_MAX
+            : c->n_blocks <= SPHRT_SINGLE_WAVE_BLOCKS ? INT32_MAX
             : bytes > (int64_t)(1 << 20) ? 64 : 0;
     return (c->order & 1) ? ~k : k;   // (block_of: reversed)
 }
@@ -2112,45 +2094,124 @@ extern "C" int sphrt_time_next_forward(void* start_event, void* stop_event) {
     return 0;
 }
 
-#define FWD_LAUNCH(KERNEL, G, B, LDS, ST, ...)                                                   \
-    do {                                                                                          \
-        if (t_fwd_start || t_fwd_stop) {                                                          \
-            hipEvent_t e0_ = t_fwd_start, e1_ = t_fwd_stop;                                       \
-            t_fwd_start = t_fwd_stop = nullptr;                                                   \
-            hipExtLaunchKernelGGL(KERNEL, G, B, (uint32_t)(LDS), ST, e0_, e1_, 0u, __VA_ARGS__);   \
-        } else {                                                                                  \
-            hipLaunchKernelGGL(KERNEL, G, B, LDS, ST, __VA_ARGS__);                               \
-        }                                                                                         \
-    } while (0)
+// The forward plan: which forward_kernel instantiation a call on elements of `elem` bytes (4, 8)
+// launches, with how much LDS and in what block order.  The one place that choice is made:
+// launch_forward dispatches from it, sphrt_forward_plan reports it.  Host code, no HIP call.
+static int forward_plan(const sphrt_csr* c, size_t elem, const void* density, int64_t n_chan,
+                        int64_t chan_stride, int64_t div, sphrt_fwd_plan* p) {
+    StageMap sm;
+    if (!stage_map(c, sm)) return fail("inconsistent brick staging fields");
+    *p = sphrt_fwd_plan{};
+    p->dense = (c->order & 4) != 0;                // (instantiations with DENSE)
+    if (p->dense && (n_chan != 1 || div > 0 || c->runs))
+        return fail("dense output ranges need one channel, no time slices and no run records");
+    // (dense output ranges read the blocks of sphrt_csr_index_dense: their count at least)
+    if (p->dense && c->n_blocks != c->n_segments / kDenseSegPerBlock + 1)
+        return fail("dense output ranges need the blocks of sphrt_csr_index_dense");
+    p->mode = div > 0 ? kFwdDynamic : kFwdGather;
+    p->tab_bytes = 4;
+    p->early_rounds = kGranEarly;
+    p->segs_per_thread = kPer;
+    p->chunk = fwd_chunk(c, elem);
+    p->elem_bytes = (int32_t)elem;
+    // The granule tables apply to static channels whose granules are 16-byte (float) / 32-byte
+    // (double) aligned; anything else takes the per-segment gather through vox.
+    const void* td = sm.on ? c->stage : density;    // what the table kernel gathers
+    const int64_t tcs = sm.on ? c->stage_cols : chan_stride;
+    const int64_t ts = c->tab_stride;
+    // (the staged output range of dense output ranges, which the granule image leaves room for)
+    const size_t ostage = p->dense ? kOutStage * elem : 0;
+    if (div > 0 || !c->loc || !c->tab || c->n_cols <= 0 || ts < 1 ||
+        (size_t)(imax64(ts, kGranEarly * kThreads) + 1) * 4 * elem + ostage > kTableLdsMax ||
+        (uintptr_t)td % (4 * elem) != 0 || (n_chan > 1 && tcs % 4 != 0))
+        return 0;
+    p->mode = kFwdTable;
+    p->tab_bytes = c->tab_bytes == 2 ? 2 : 4;
+    // Early granule DMA (forward_kernel EDMA) needs whole granules only: no partial last granule.
+    p->edma = table_cols(c) % 4 == 0;
+    p->runs = c->runs != nullptr;
+    // (the half-table kernel exists for float64 and the default segments per thread: table_kernel)
+    p->half = elem == 8 && p->edma && (size_t)(ts + 1) * 4 * elem > kHalfTabMinLds &&
+              ts <= 2 * kHalfTab && half_tables_on();
+    // early DMA rounds: as many 256-entry chunks as the largest table needs (at most
+    // kGranEarly), so neither the LDS image nor the unconditional early DMAs exceed the
+    // tables (C4's time-paired adjoint: 448-entry tables, 3 -> 2 chunks)
+    if (p->edma && !p->half)
+        p->early_rounds = ts <= kThreads ? 1 : ts <= 2 * kThreads ? 2 : kGranEarly;
+    const int64_t image = p->half   ? kHalfTab      // granules staged at a time
+                          : p->edma ? imax64(ts, (int64_t)p->early_rounds * kThreads) : ts;
+    p->lds_bytes = (int32_t)((size_t)(image + 1) * 4 * elem + ostage);   // (+ the zero granule)
+    p->fallback = c->n_fallback > 0;
+    return 0;
+}
+
+template <typename T, typename L, typename TabT>
+using FwdKernel = void (*)(const int64_t*, const int32_t*, const uint16_t*, const TabT*, const L*,
+                           const int32_t*, const int32_t*, const T*, int64_t, int64_t, int64_t, T*,
+                           int64_t, int64_t, int64_t, int64_t, int64_t, int, int, const int32_t*);
+
+// The table-mode instantiation of a plan: <EDMA, HALF, GE> in table_kernel, <RUNS, DENSE> here.
+template <typename T, typename L, typename TabT, int P, bool E, bool H, int G>
+static FwdKernel<T, L, TabT> table_kernel_rd(const sphrt_fwd_plan& p) {
+    if (p.dense) return forward_kernel<T, L, kFwdTable, TabT, E, P, false, H, true, G>;
+    if (p.runs) return forward_kernel<T, L, kFwdTable, TabT, E, P, true, H, false, G>;
+    return forward_kernel<T, L, kFwdTable, TabT, E, P, false, H, false, G>;
+}
+
+template <typename T, typename L, typename TabT, int P>
+static FwdKernel<T, L, TabT> table_kernel(const sphrt_fwd_plan& p) {
+    if constexpr (sizeof(T) == 8 && P == kPer)      // (forward_plan: half tables for these only)
+        if (p.half) return table_kernel_rd<T, L, TabT, P, true, true, kGranEarly>(p);
+    if (!p.edma) return table_kernel_rd<T, L, TabT, P, false, false, kGranEarly>(p);
+    switch (p.early_rounds) {
+    case 1: return table_kernel_rd<T, L, TabT, P, true, false, 1>(p);
+    case 2: return table_kernel_rd<T, L, TabT, P, true, false, 2>(p);
+    default: return table_kernel_rd<T, L, TabT, P, true, false, kGranEarly>(p);
+    }
+}
+
+// One launch of a forward.  main: the plan's kernel, with its LDS and run records, bracketed by
+// the events of sphrt_time_next_forward if any; else the gather over the blocks it skipped.
+template <typename T, typename L, typename TabT>
+static void fwd_launch(FwdKernel<T, L, TabT> kernel, bool main, const sphrt_csr* c,
+                       const sphrt_fwd_plan& p, const L* len, const T* density, int64_t n_chan,
+                       int64_t chan_stride, int64_t div, T* out, int64_t ocs, hipStream_t st) {
+    const dim3 grid((unsigned)c->n_blocks), block(kPass / p.segs_per_thread);
+    const int64_t cols = main && p.mode == kFwdTable ? table_cols(c) : c->n_cols;
+    const uint32_t lds = main ? (uint32_t)p.lds_bytes : 0u;
+    const int32_t* runs = main && p.runs ? c->runs : nullptr;
+#define FWD_ARGS c->blocks, c->vox, c->loc, (const TabT*)c->tab, len, c->row_ray, c->empty_ray,    \
+                 density, n_chan, chan_stride, div, out, ocs, c->n_rays, c->n_segments, cols,      \
+                 c->tab_stride, (int)p.chunk, /* fallback_only */ main ? 0 : 1, runs
+    hipEvent_t e0 = main ? t_fwd_start : nullptr, e1 = main ? t_fwd_stop : nullptr;
+    if (e0 || e1) t_fwd_start = t_fwd_stop = nullptr;      // (consumed by this launch)
+    if (e0 || e1) hipExtLaunchKernelGGL(kernel, grid, block, lds, st, e0, e1, 0u, FWD_ARGS);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, st, FWD_ARGS);
+#undef FWD_ARGS
+}
 
 template <typename T, typename L>
 static int launch_forward(const sphrt_csr* c, const L* len, const T* density, int64_t n_chan,
                           int64_t chan_stride, int64_t div, T* out, int64_t ocs, void* stream) {
     constexpr int P = kPer;                         // segments per thread
-    const dim3 grid((unsigned)c->n_blocks), block(kPass / P);
+    sphrt_fwd_plan p;
+    if (int e = forward_plan(c, sizeof(T), density, n_chan, chan_stride, div, &p)) return e;
+    // (dense workgroups zero their ranges with 16-byte stores placed by element index: zero_range)
+    if (p.dense && (uintptr_t)out % 16 != 0)
+        return fail("dense output ranges need a 16-byte aligned output");
     StreamGuard guard(stream);
     hipStream_t st = (hipStream_t)stream;
-    const int chunk = fwd_chunk(c, sizeof(T));
-    StageMap sm;
-    if (!stage_map(c, sm)) return fail("inconsistent brick staging fields");
-#define FWD_ARGS(TabT, D, CS, COLS) c->blocks, c->vox, c->loc, (const TabT*)c->tab, len,    \
-                       c->row_ray, c->empty_ray, D, n_chan, CS, div, out, ocs, c->n_rays,          \
-                       c->n_segments, COLS, c->tab_stride, chunk
-    if ((c->order & 4) && (n_chan != 1 || div > 0 || c->runs))
-        return fail("dense output ranges need one channel, no time slices and no run records");
-    const bool dense = (c->order & 4) != 0;        // (instantiations with DENSE)
-    // (dense output ranges read the blocks of sphrt_csr_index_dense: their count at least)
-    if (dense && c->n_blocks != c->n_segments / kDenseSegPerBlock + 1)
-        return fail("dense output ranges need the blocks of sphrt_csr_index_dense");
-    // (their workgroups zero their ranges with 16-byte stores placed by element index: zero_range)
-    if (dense && (uintptr_t)out % 16 != 0)
-        return fail("dense output ranges need a 16-byte aligned output");
-    const T* td = sm.on ? (const T*)c->stage : density;      // what the table kernel gathers
-    const int64_t tcs = sm.on ? c->stage_cols : chan_stride;
-    if (div > 0) {
-        FWD_LAUNCH((forward_kernel<T, L, kFwdDynamic, int32_t, false, P>), grid, block, 0, st,
-                   FWD_ARGS(int32_t, density, chan_stride, c->n_cols), 0, (const int32_t*)nullptr);
-    } else if (use_tables(c, td, n_chan, tcs, div)) {
+    // the kernel without tables: a launch of its own, or after the tables for their fallback blocks
+    const FwdKernel<T, L, int32_t> plain =
+        p.mode == kFwdDynamic ? forward_kernel<T, L, kFwdDynamic, int32_t, false, P>
+        : p.dense ? forward_kernel<T, L, kFwdGather, int32_t, false, P, false, false, true>
+                  : forward_kernel<T, L, kFwdGather, int32_t, false, P>;
+    auto launch = [&](auto kernel, bool main, const T* d, int64_t cs) {
+        fwd_launch<T, L>(kernel, main, c, p, len, d, n_chan, cs, div, out, ocs, st);
+    };
+    if (p.mode == kFwdTable) {
+        StageMap sm;
+        stage_map(c, sm);                           // (valid: forward_plan)
         if (sm.on && (!c->stage || (int64_t)sizeof(T) * n_chan * c->stage_cols > c->stage_bytes))
             return fail("brick stage buffer missing or too small for this call");
         if (sm.on && !c->stage_packed) {   // natural -> brick layout, every channel
@@ -2160,78 +2221,17 @@ static int launch_forward(const sphrt_csr* c, const L* len, const T* density, in
                                n_chan, (uint32_t)c->stage_shape[0], sm, c->stage_cols, (T*)c->stage);
             if (int e = check_launch("stage_pack_kernel")) return e;
         }
-        const bool edma = early_dma(c);
-        // float64 tables that leave fewer than 4 workgroups per CU (over 40 KB of LDS): half
-        // tables, 5 per CU (C5 forward f64 62.1 -> 53.0 us, transposed adjoint 58.8 -> 53.7 us).
-        // Not below: C3's 34.8 KB tables (4 per CU) measured 364 -> 383 us with halves (more
-        // resident workgroups, more L2 misses; few of its tables even need the second phase).
-        // (the half-table kernel exists for the default segments per thread only: P == kPer)
-        const bool half = sizeof(T) == 8 && P == kPer && edma &&
-                          (size_t)(c->tab_stride + 1) * 32 > 40 * 1024 &&
-                          c->tab_stride <= 2 * kHalfTab && half_tables_on();
-        // early DMA rounds: as many 256-entry chunks as the largest table needs (at most
-        // kGranEarly), so neither the LDS image nor the unconditional early DMAs exceed the
-        // tables (C4's time-paired adjoint: 448-entry tables, 3 -> 2 chunks)
-        const int ge = c->tab_stride <= kThreads ? 1 : c->tab_stride <= 2 * kThreads ? 2 : 3;
-        size_t lds = (size_t)((half ? kHalfTab
-                               : edma ? imax64(c->tab_stride, (int64_t)ge * kThreads)
-                                      : c->tab_stride) + 1) * 4 * sizeof(T);   // + zero granule
-        if (dense) lds += (size_t)kOutStage * sizeof(T);       // the staged output range
-#define FWD_TABLE(TabT, E, R, H, D, G)                                                      \
-        FWD_LAUNCH((forward_kernel<T, L, kFwdTable, TabT, E, P, R, H, D, G>), grid, block, lds, \
-                   st, FWD_ARGS(TabT, td, tcs, table_cols(c)), 0, c->runs)
-#define FWD_TABLE_R(TabT, E, H, G)                                                          \
-        do {                                                                                      \
-            if (dense) FWD_TABLE(TabT, E, false, H, true, G);                               \
-            else if (c->runs) FWD_TABLE(TabT, E, true, H, false, G);                        \
-            else FWD_TABLE(TabT, E, false, H, false, G);                                    \
-        } while (0)
-#define FWD_TABLE_E(TabT)                                                                   \
-        do {                                                                                      \
-            if (half) {                                                                           \
-                if constexpr (sizeof(T) == 8 && P == kPer) {                                      \
-                    FWD_TABLE_R(TabT, true, true, kGranEarly);                                    \
-                }                                                                                 \
-            } else if (edma && ge == 1) {                                                         \
-                FWD_TABLE_R(TabT, true, false, 1);                                                \
-            } else if (edma && ge == 2) {                                                         \
-                FWD_TABLE_R(TabT, true, false, 2);                                                \
-            } else if (edma) {                                                                    \
-                FWD_TABLE_R(TabT, true, false, kGranEarly);                                       \
-            } else {                                                                              \
-                FWD_TABLE_R(TabT, false, false, kGranEarly);                                      \
-            }                                                                                     \
-        } while (0)
-        if (c->tab_bytes == 2) {
-            FWD_TABLE_E(uint16_t);
-        } else {
-            FWD_TABLE_E(int32_t);
-        }
-#undef FWD_TABLE_E
-#undef FWD_TABLE_R
-#undef FWD_TABLE
-        if (c->n_fallback > 0) {   // (natural vox, natural density)
+        const T* td = sm.on ? (const T*)c->stage : density;   // what the table kernel gathers
+        const int64_t tcs = sm.on ? c->stage_cols : chan_stride;
+        if (p.tab_bytes == 2) launch(table_kernel<T, L, uint16_t, P>(p), true, td, tcs);
+        else launch(table_kernel<T, L, int32_t, P>(p), true, td, tcs);
+        if (p.fallback) {   // (natural vox, natural density)
             if (int e = check_launch("forward_kernel<table>")) return e;
-            if (dense)
-                hipLaunchKernelGGL((forward_kernel<T, L, kFwdGather, int32_t, false, P, false, false,
-                                                   true>), grid, block, 0, st,
-                                   FWD_ARGS(int32_t, density, chan_stride, c->n_cols), 1, nullptr);
-            else
-                hipLaunchKernelGGL((forward_kernel<T, L, kFwdGather, int32_t, false, P>), grid, block,
-                                   0, st, FWD_ARGS(int32_t, density, chan_stride, c->n_cols), 1,
-                                   nullptr);
+            launch(plain, false, density, chan_stride);
         }
     } else {
-        if (dense)
-            FWD_LAUNCH((forward_kernel<T, L, kFwdGather, int32_t, false, P, false, false, true>), grid,
-                       block, 0, st, FWD_ARGS(int32_t, density, chan_stride, c->n_cols), 0,
-                       (const int32_t*)nullptr);
-        else
-            FWD_LAUNCH((forward_kernel<T, L, kFwdGather, int32_t, false, P>), grid, block, 0, st,
-                       FWD_ARGS(int32_t, density, chan_stride, c->n_cols), 0,
-                       (const int32_t*)nullptr);
+        launch(plain, true, density, chan_stride);
     }
-#undef FWD_ARGS
     return check_launch(sizeof(T) == 4 ? "forward_kernel<f32>" : "forward_kernel<f64>");
 }
 
@@ -2251,6 +2251,16 @@ extern "C" int sphrt_forward_f64(const sphrt_csr* c, const double* density, int6
     if (!c->len) return fail("missing segment lengths");
     if (c->n_rays == 0) return 0;
     return launch_forward(c, c->len, density, n_chan, chan_stride, div, out, ocs, stream);
+}
+
+extern "C" int sphrt_forward_plan(const sphrt_csr* c, int elem_bytes, const void* density,
+                                  int64_t n_chan, int64_t chan_stride, int64_t div,
+                                  sphrt_fwd_plan* out) {
+    if (elem_bytes != 4 && elem_bytes != 8)
+        return fail("elem_bytes must be 4 (float32) or 8 (float64), not %d", elem_bytes);
+    if (!out) return fail("null forward plan");
+    if (int e = check_csr(c, n_chan, div)) return e;
+    return forward_plan(c, (size_t)elem_bytes, density, n_chan, chan_stride, div, out);
 }
 
 extern "C" int sphrt_adjoint_accumulate(const sphrt_csr* c, const void* y, int y_is_f64,

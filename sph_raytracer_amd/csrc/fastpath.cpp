@@ -130,7 +130,7 @@ PyObject* py_add(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
     Py_RETURN_NONE;
 }
 
-constexpr int64_t kAlternateMinBlocks = 256 * 6;   // raytracer._ALTERNATE_MIN_BLOCKS
+constexpr int64_t kAlternateMinBlocks = SPHRT_SINGLE_WAVE_BLOCKS;   // raytracer._ALTERNATE_MIN_BLOCKS
 
 // forward(capsule, density) -> Tensor, or None when no binding applies
 PyObject* py_forward(PyObject*, PyObject* const* args, Py_ssize_t nargs) {

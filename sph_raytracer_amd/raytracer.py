@@ -629,7 +629,7 @@ def _local_tables(lib, desc, blocks, nblocks, total, dev, stream, staged=None):
 _BRICK = (4, 2, 4)   # (r, e, a) voxels per staging brick: 32 = one 128-byte float line
 # (4, 2, 4) over round 1's (2, 4, 4): C3 forward f32 214.5 -> 204.1 us, f64 350.4 -> 333.5 us, C5
 # unchanged (27.7 / 45.3 us); 11 shapes swept in profiles/r02_brick_sweep.jsonl.
-_SINGLE_WAVE_BLOCKS = 256 * 6   # forward workgroups resident at once (256 CUs x 6)
+_SINGLE_WAVE_BLOCKS = _lib.SINGLE_WAVE_BLOCKS   # forward workgroups resident at once (256 CUs x 6)
 
 
 _HEAD32 = -2 ** 31      # bit 31 of an int32 (the row-head flag of vox)
@@ -755,7 +755,7 @@ def _stage_bytes(desc, n_chan, elem):
 # of the ones it evicted first.  Same results.  Measured on repeated forwards (tools/prof, MI355X):
 # C3 f32 233 -> 213 us, f64 364 -> 350 us, C5 f32 29.3 -> 28.3 us; one-wave launches (C2) gain
 # nothing and keep their order.  The C++ fast path (csrc/fastpath.cpp) applies the same rule.
-_ALTERNATE_MIN_BLOCKS = 256 * 6
+_ALTERNATE_MIN_BLOCKS = _lib.SINGLE_WAVE_BLOCKS
 
 
 def _alternate(desc):
@@ -1435,8 +1435,8 @@ class Operator:
         reports): 0 = granule tables staged in LDS, 1 = per-segment gathers, 2 = time slices;
         the last flag: float64 half tables."""
         n_chan, div, _ = self._layout(d.shape)
-        c, n_chan, _, div = self._launch_args(d, n_chan, div)
-        return self._kernel_name_for(c, d, n_chan, div)
+        c, n_chan, cs, div = self._launch_args(d, n_chan, div)
+        return self._kernel_name_for(c, d, n_chan, div, cs)
 
     def _adjoint_kernel_name(self, d):
         """The instantiation the adjoint of a density like `d` runs (the transposed CSR's
@@ -1449,28 +1449,18 @@ class Operator:
         return self._kernel_name_for(c, d, 1, 0)
 
     @staticmethod
-    def _kernel_name_for(c, d, n_chan, div):
-        t = 'float, float' if d.dtype == tr.float32 else 'double, double'
-        es = d.element_size()
-        dense = 'true' if c.order & 4 else 'false'     # (dense output ranges, sphrt.h order)
-        aligned = d.data_ptr() % (4 * es) == 0 and (n_chan == 1 or d[0].numel() % 4 == 0)
-        extra = 2560 * es if c.order & 4 else 0          # (apply.hip kOutStage)
-        table = (c.loc and div == 0 and 0 < c.tab_stride
-                 and (max(c.tab_stride, 768) + 1) * 4 * es + extra <= 64 * 1024
-                 and (c.stage_shape[0] > 0 or aligned))
-        if table:   # early granule DMA whenever the table columns are whole granules
-            cols = c.stage_cols if c.stage_shape[0] > 0 else c.n_cols
-            edma = 'true' if cols % 4 == 0 else 'false'
-            tabt = 'unsigned short' if c.tab_bytes == 2 else 'int'
-            runs = 'true' if c.runs else 'false'
-            # float64 half tables (apply.hip kHalfTab = 768 granules per phase)
-            half = (es == 8 and edma == 'true' and (c.tab_stride + 1) * 32 > 40 * 1024
-                    and c.tab_stride <= 1536 and os.environ.get('SPHRT_FWD_HALF', '1') != '0')
-            # early DMA rounds: 256-entry chunks of the largest table (apply.hip launch_forward)
-            ge = 3 if half or edma == 'false' else min(3, max(1, -(-c.tab_stride // 256)))
-            return (f'forward_kernel<{t}, 0, {tabt}, {edma}, 8, {runs}, '
-                    f'{"true" if half else "false"}, {dense}, {ge}>')
-        return f'forward_kernel<{t}, {2 if div else 1}, int, false, 8, false, false, {dense}, 3>'
+    def _kernel_name_for(c, d, n_chan, div, chan_stride=None):
+        """sphrt_forward_plan's choice for `c` on `d` as a name (chan_stride None: contiguous d)."""
+        p = _lib.ForwardPlan()
+        cs = d.numel() // n_chan if chan_stride is None else chan_stride
+        _lib.check(_lib.load().sphrt_forward_plan(ctypes.byref(c), d.element_size(), d.data_ptr(),
+                                                  n_chan, cs, div, ctypes.byref(p)),
+                   'sphrt_forward_plan')
+        t = 'float, float' if p.elem_bytes == 4 else 'double, double'
+        tabt = 'unsigned short' if p.tab_bytes == 2 else 'int'
+        edma, runs, half, dense = (('false', 'true')[f] for f in (p.edma, p.runs, p.half, p.dense))
+        return (f'forward_kernel<{t}, {p.mode}, {tabt}, {edma}, {p.segs_per_thread}, {runs}, '
+                f'{half}, {dense}, {p.early_rounds}>')
 
     def _apply_forward(self, density):
         with tr.cuda.device(self._cdev):      # launches and allocations on the operator's GPU

@@ -345,7 +345,8 @@ def test_library_builds_and_exports_header():
     for name, val in (('SPHRT_ROW_HEAD', _lib.ROW_HEAD), ('SPHRT_BLOCK_FIELDS', _lib.BLOCK_FIELDS),
                       ('SPHRT_LOC_HEAD', _lib.LOC_HEAD), ('SPHRT_TRACE_F32', _lib.TRACE_F32),
                       ('SPHRT_TRACE_INVALID', _lib.TRACE_INVALID),
-                      ('SPHRT_TRACE_FRESH_RAYS', _lib.TRACE_FRESH_RAYS)):
+                      ('SPHRT_TRACE_FRESH_RAYS', _lib.TRACE_FRESH_RAYS),
+                      ('SPHRT_SINGLE_WAVE_BLOCKS', _lib.SINGLE_WAVE_BLOCKS)):
         m = re.search(rf'#define {name} (0x[0-9a-fA-F]+|\d+)', hdr)
         assert m and int(m.group(1).rstrip('u'), 0) == val, name
     lib = _lib.load()
@@ -437,6 +438,152 @@ def test_staged_and_reference_trace_argument_checks():
         assert word in lib.sphrt_last_error().lower(), lib.sphrt_last_error()
 
 
+def _plan_csr(tab_stride, n_cols=64, tab_bytes=4, order=0, runs=False, n_fallback=0,
+              stage_shape=None, n_blocks=1):
+    """A complete descriptor whose pointers are never dereferenced (sphrt_forward_plan reads
+    the fields only): one block, granule tables of `tab_stride` entries."""
+    from sph_raytracer_amd import _lib
+    p = 64
+    c = _lib.CSR()
+    c.n_rays, c.n_segments, c.n_blocks = 10, 100, n_blocks
+    c.row_ptr = c.vox = c.len = c.len32 = c.row_ray = c.blocks = c.empty_ray = c.loc = c.tab = p
+    c.tab_stride, c.tab_bytes, c.n_fallback, c.order = tab_stride, tab_bytes, n_fallback, order
+    c.n_cols = n_cols
+    c.runs = p if runs else None
+    if stage_shape is not None:            # bricks of (1, 1, 4) voxels, no stage buffer yet
+        c.stage_shape[:] = stage_shape
+        c.stage_brick[:] = (1, 1, 4)
+        c.n_cols = stage_shape[0] * stage_shape[1] * stage_shape[2]
+        c.stage_cols = stage_shape[0] * stage_shape[1] * ((stage_shape[2] + 3) // 4 * 4)
+    return c
+
+
+def test_forward_plan(monkeypatch):
+    """sphrt_forward_plan is where the forward kernel is chosen (launch_forward dispatches from
+    the same record) and Operator._kernel_name_for only formats it: named descriptors pinned to
+    their plan fields and name strings, one per branch of the rule (table / gather / time
+    slices, table width, early DMA and its rounds, half tables and their switch, dense output
+    ranges, run records, fallback launch, the LDS limits on both sides, alignment of the density
+    and of the channel stride, a brick-staged CSR), then the refusals, each with a message in
+    sphrt_last_error.  (No device call.)"""
+    from sph_raytracer_amd import _lib
+    from sph_raytracer_amd.raytracer import Operator
+    lib = _lib.load()
+    monkeypatch.delenv('SPHRT_FWD_HALF', raising=False)
+    base = {4: tr.zeros(64, dtype=tr.float32), 8: tr.zeros(64, dtype=tr.float64)}
+    assert all(b.data_ptr() % 64 == 0 for b in base.values())
+    i32max = 2 ** 31 - 1
+    f, d = 'float, float', 'double, double'
+    # name: (descriptor, elem, first element, (n_chan, channel stride), div, SPHRT_FWD_HALF,
+    #        plan fields that differ from a gather plan, kernel name)
+    gather = dict(mode=1, tab_bytes=4, edma=0, runs=0, half=0, dense=0, early_rounds=3,
+                  segs_per_thread=8, fallback=0, lds_bytes=0, chunk=i32max)
+    cases = {
+        'f32 table, 2 rounds': (
+            _plan_csr(512), 4, 0, (1, 24), 0, None,
+            dict(mode=0, edma=1, early_rounds=2, lds_bytes=513 * 16),
+            f'forward_kernel<{f}, 0, int, true, 8, false, false, false, 2>'),
+        'time-paired dense 448-entry table': (
+            _plan_csr(448, order=2 | 4), 4, 0, (1, 24), 0, None,
+            dict(mode=0, edma=1, dense=1, early_rounds=2, lds_bytes=513 * 16 + 2560 * 4),
+            f'forward_kernel<{f}, 0, int, true, 8, false, false, true, 2>'),
+        'f64 half table': (
+            _plan_csr(1408), 8, 0, (1, 24), 0, None,
+            dict(mode=0, edma=1, half=1, lds_bytes=769 * 32),
+            f'forward_kernel<{d}, 0, int, true, 8, false, true, false, 3>'),
+        'f64 half table switched off': (
+            _plan_csr(1408), 8, 0, (1, 24), 0, '0',
+            dict(mode=0, edma=1, lds_bytes=1409 * 32),
+            f'forward_kernel<{d}, 0, int, true, 8, false, false, false, 3>'),
+        'f64 below the half-table threshold': (
+            _plan_csr(1279), 8, 0, (1, 24), 0, None,
+            dict(mode=0, edma=1, lds_bytes=1280 * 32),
+            f'forward_kernel<{d}, 0, int, true, 8, false, false, false, 3>'),
+        'uint16 table with runs, 1 round': (
+            _plan_csr(256, tab_bytes=2, runs=True), 4, 0, (1, 24), 0, None,
+            dict(mode=0, tab_bytes=2, edma=1, runs=1, early_rounds=1, lds_bytes=257 * 16),
+            f'forward_kernel<{f}, 0, unsigned short, true, 8, true, false, false, 1>'),
+        'misaligned density': (
+            _plan_csr(512), 4, 1, (1, 24), 0, None, {},
+            f'forward_kernel<{f}, 1, int, false, 8, false, false, false, 3>'),
+        'time slices': (
+            _plan_csr(512), 8, 0, (1, 24), 5, None, dict(mode=2),
+            f'forward_kernel<{d}, 2, int, false, 8, false, false, false, 3>'),
+        'table with fallback blocks, partial granule': (
+            _plan_csr(513, n_cols=42, n_fallback=1), 4, 0, (1, 24), 0, None,
+            dict(mode=0, fallback=1, lds_bytes=514 * 16),
+            f'forward_kernel<{f}, 0, int, false, 8, false, false, false, 3>'),
+        'f64 dense at the LDS limit': (
+            _plan_csr(1407, order=4), 8, 0, (1, 24), 0, None,
+            dict(mode=0, edma=1, half=1, dense=1, lds_bytes=769 * 32 + 2560 * 8),
+            f'forward_kernel<{d}, 0, int, true, 8, false, true, true, 3>'),
+        'f64 dense past the LDS limit': (
+            _plan_csr(1408, order=4), 8, 0, (1, 24), 0, None, dict(dense=1),
+            f'forward_kernel<{d}, 1, int, false, 8, false, false, true, 3>'),
+        'f32 largest table': (
+            _plan_csr(4095), 4, 0, (1, 24), 0, None,
+            dict(mode=0, edma=1, lds_bytes=4096 * 16),
+            f'forward_kernel<{f}, 0, int, true, 8, false, false, false, 3>'),
+        'f32 table too large': (
+            _plan_csr(4096), 4, 0, (1, 24), 0, None, {},
+            f'forward_kernel<{f}, 1, int, false, 8, false, false, false, 3>'),
+        'three channels, whole-granule stride': (
+            _plan_csr(768), 4, 0, (3, 8), 0, None,
+            dict(mode=0, edma=1, lds_bytes=769 * 16),
+            f'forward_kernel<{f}, 0, int, true, 8, false, false, false, 3>'),
+        'three channels, stride 6': (
+            _plan_csr(768), 4, 0, (3, 6), 0, None, {},
+            f'forward_kernel<{f}, 1, int, false, 8, false, false, false, 3>'),
+        'brick-staged, no stage yet, misaligned density': (
+            _plan_csr(257, stage_shape=(3, 2, 7)), 8, 1, (1, 24), 0, None,
+            dict(mode=0, edma=1, early_rounds=2, lds_bytes=513 * 32),
+            f'forward_kernel<{d}, 0, int, true, 8, false, false, false, 2>'),
+        'several waves, reversed order': (
+            _plan_csr(512, n_cols=1 << 19, order=1, n_blocks=_lib.SINGLE_WAVE_BLOCKS + 1), 4, 0,
+            (1, 24), 0, None,
+            dict(mode=0, edma=1, early_rounds=2, lds_bytes=513 * 16, chunk=~64),
+            f'forward_kernel<{f}, 0, int, true, 8, false, false, false, 2>'),
+    }
+    for name, (c, elem, first, (n_chan, cs), div, env, fields, kernel) in cases.items():
+        if env is None:
+            monkeypatch.delenv('SPHRT_FWD_HALF', raising=False)
+        else:
+            monkeypatch.setenv('SPHRT_FWD_HALF', env)
+        x = base[elem][first:first + n_chan * cs].view(n_chan, cs)
+        p = _lib.ForwardPlan()
+        assert lib.sphrt_forward_plan(ctypes.byref(c), elem, x.data_ptr(), n_chan, cs, div,
+                                      ctypes.byref(p)) == 0, (name, lib.sphrt_last_error())
+        want = dict(gather, elem_bytes=elem, **fields)
+        assert {k: getattr(p, k) for k in want} == want, name
+        assert Operator._kernel_name_for(c, x if n_chan > 1 else x[0], n_chan, div) == kernel, name
+        assert Operator._kernel_name_for(c, x, n_chan, div, cs) == kernel, name
+    monkeypatch.delenv('SPHRT_FWD_HALF', raising=False)
+    x, p = base[4].data_ptr(), _lib.ForwardPlan()
+
+    def plan(c, elem=4, n_chan=1, div=0, out=p):
+        return lib.sphrt_forward_plan(ctypes.byref(c), elem, x, n_chan, 24, div,
+                                      ctypes.byref(out) if out is not None else None)
+
+    staged = _plan_csr(512, stage_shape=(3, 2, 7))
+    staged.stage_cols += 4
+    refusals = [
+        (lambda: plan(_plan_csr(512), elem=2), b'elem_bytes'),
+        (lambda: plan(_plan_csr(512), out=None), b'null'),
+        (lambda: plan(_lib.CSR()), b'incomplete'),
+        (lambda: plan(_plan_csr(512), n_chan=3, div=5), b'ray_chan_div'),
+        (lambda: plan(_plan_csr(512, order=4, runs=True)), b'dense output ranges need one'),
+        (lambda: plan(_plan_csr(512, order=4), n_chan=2), b'dense output ranges need one'),
+        (lambda: plan(_plan_csr(512, order=4), div=5), b'dense output ranges need one'),
+        (lambda: plan(_plan_csr(512, order=4, n_blocks=2)), b'sphrt_csr_index_dense'),
+        (lambda: plan(staged), b'staging'),
+    ]
+    for call, word in refusals:
+        assert call() != 0
+        assert word in lib.sphrt_last_error(), lib.sphrt_last_error()
+    with pytest.raises(RuntimeError, match='dense output ranges'):
+        Operator._kernel_name_for(_plan_csr(512, order=4, runs=True), base[4][:24], 1, 0)
+
+
 def test_fastpath_entry_builds_and_declines_foreign_inputs():
     """csrc/fastpath.cpp (the CPython entry for steady-state Operator calls) builds against the
     installed torch, loads, and returns None for anything it has no binding for (CPU tensors,
@@ -521,7 +668,7 @@ def test_compute_device_resolution():
 
 
 def test_ctypes_structs_match_the_c_header(tmp_path):
-    """The ctypes mirrors in _lib (GridDesc, RayBatch, CSR) have the C ABI layout of
+    """The ctypes mirrors in _lib (GridDesc, RayBatch, CSR, ForwardPlan) have the C ABI layout of
     include/sphrt.h: every field at the C offset, same struct size (gcc on the header)."""
     import shutil
     import subprocess
@@ -531,7 +678,7 @@ def test_ctypes_structs_match_the_c_header(tmp_path):
         pytest.skip('gcc not available')
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pairs = [('sphrt_grid_desc', _lib.GridDesc), ('sphrt_rays', _lib.RayBatch),
-             ('sphrt_csr', _lib.CSR)]
+             ('sphrt_csr', _lib.CSR), ('sphrt_fwd_plan', _lib.ForwardPlan)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "sphrt.h"', 'int main(void) {']
     for cname, py in pairs:
         lines.append(f'printf("{cname} sizeof %zu\\n", sizeof({cname}));')
