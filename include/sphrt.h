@@ -483,6 +483,18 @@ int sphrt_trace_integrate_f64(const sphrt_plan *plan, const sphrt_rays *rays,
                               const double *density, int64_t n_chan, int64_t chan_stride,
                               int64_t ray_chan_div, double *out, int64_t out_chan_stride,
                               void *workspace, size_t workspace_size, void *stream);
+/* fused no-store adjoint: trace + scatter, nothing persisted.  acc as sphrt_adjoint_accumulate
+ * (float64, zeroed and owned by the caller; float64 atomics, so sums are not bitwise
+ * reproducible): acc[c*chan_stride + vox] += y[c*y_chan_stride + i] * len for every segment of
+ * ray i, or with ray_chan_div > 0 (n_chan == 1) acc[(i / ray_chan_div)*chan_stride + vox] +=
+ * y[i] * len.  Rays that miss the grid write nothing.  Fails on the host, before any launch, on a
+ * null y or acc, a chan_stride below the grid's voxel count and a workspace smaller than
+ * sphrt_trace_workspace_bytes.  Replaces Operator.T (raytracer.py:715-748) over a trace that is
+ * never stored. */
+int sphrt_trace_backproject_f64(const sphrt_plan *plan, const sphrt_rays *rays, const double *y,
+                                int64_t n_chan, int64_t y_chan_stride, int64_t ray_chan_div,
+                                double *acc, int64_t chan_stride,
+                                void *workspace, size_t workspace_size, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2,8 +2,8 @@
 
     from sph_raytracer_amd import SphericalGrid, ConeRectGeom, Operator
 """
-from .raytracer import Operator
+from .raytracer import MatrixFreeOperator, Operator, back_project, line_integrals
 from .geometry import *  # noqa: F401,F403
 from .geometry import __all__ as _geometry_all
 
-__all__ = ['Operator'] + list(_geometry_all)
+__all__ = ['Operator', 'MatrixFreeOperator', 'back_project', 'line_integrals'] + list(_geometry_all)

@@ -14,8 +14,9 @@
 //   3. the sorted list is scanned (forward fill of the r/e/a rows: in registers, lane-major,
 //      for lists of <= 512 entries), differenced and the non-zero in-grid segments compacted, in
 //      order, back into LDS;
-//   4. depending on MODE the segments are counted, copied to the CSR, or integrated against
-//      the density right away (no-store mode).
+//   4. depending on MODE the segments are counted, copied to the CSR, integrated against the
+//      density right away (no-store forward), or scattered into a float64 accumulator weighted
+//      by the ray's value (no-store adjoint).
 // Nothing of size K ever reaches HBM.
 //
 // Exact ties.  The reference orders equal distances the way libstdc++'s introsort happens to
@@ -36,8 +37,11 @@ namespace sphrt {
 // COUNT / FILL: the two-pass trace (counts, then segments at row_ptr).  BOUND (screen only) and
 // EMIT: the one-pass trace — an upper bound of every ray's segment count from its geometry, then
 // one pass that writes each ray's segments into its bounded slot of a staging CSR (compacted
-// afterwards).  INTEGRATE: the no-store forward.
-enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4 };
+// afterwards).  INTEGRATE: the no-store forward.  SCATTER: the no-store adjoint — the same trace
+// with the last step reversed, acc[vox] += y[ray] * len in float64 atomics instead of
+// out[ray] = sum rho[vox] * len.
+enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4,
+       MODE_SCATTER = 5 };
 constexpr int kNone = 0x7fffffff;  // "no update" in the forward-fill scans
 constexpr int kWavesPerBlock = 4;
 
@@ -411,10 +415,11 @@ struct TraceOut {
     const int64_t* row_ptr;   // FILL
     int32_t* vox;
     double* len;
-    const T* density;         // INTEGRATE
+    const T* density;         // INTEGRATE; SCATTER: y, its channels out_chan_stride apart
     int64_t n_chan, chan_stride, ray_chan_div;
     T* out;
     int64_t out_chan_stride;
+    double* acc;              // SCATTER: the caller's zeroed accumulator, channels chan_stride apart
     unsigned long long* n_deferred;  // workspace: deferred-ray counter
     int64_t* deferred;               // workspace: deferred ray ids
     unsigned* n_hits;                // workspace: screened hit-ray counter
@@ -440,6 +445,28 @@ __device__ __forceinline__ int64_t emit_slot(const TraceOut<T>& o, int64_t ray, 
     if (cnt <= cap) return b0;
     if (leader) atomicAdd(o.n_over, 1ull);
     return -1;
+}
+
+// SCATTER: a ray's compacted segments (seg_vox, seg_len: nseg of them, in LDS) and its head
+// segment (hlen in voxel hvox, when `head`) added into the accumulator by the whole wave — every
+// channel's y[c][ray] (static, multichannel), or y[ray] into time slice ray / ray_chan_div.
+template <typename T>
+__device__ __forceinline__ void scatter_segments(const TraceOut<T>& o, int64_t ray, int lane,
+                                                 int nseg, const int32_t* seg_vox,
+                                                 const double* seg_len, bool head, int hvox,
+                                                 double hlen) {
+    int64_t c_lo = 0, c_hi = o.n_chan;
+    if (o.ray_chan_div > 0) {
+        c_lo = ray / o.ray_chan_div;
+        c_hi = c_lo + 1;
+    }
+    for (int64_t c = c_lo; c < c_hi; ++c) {
+        const int64_t yc = o.ray_chan_div > 0 ? 0 : c;
+        const double yv = (double)o.density[yc * o.out_chan_stride + ray];
+        double* acc = o.acc + c * o.chan_stride;
+        if (head && lane == 0) atomicAdd(acc + hvox, yv * hlen);
+        for (int q = lane; q < nseg; q += 64) atomicAdd(acc + seg_vox[q], yv * seg_len[q]);
+    }
 }
 
 // region rows a candidate updates: bit0 r, bit1 e, bit2 a (start entry: all)
@@ -1010,6 +1037,9 @@ __device__ void trace_one(const GridDev& G, const RayGeo& g, const double t1c_o,
             o.vox[r0 + head + q] = seg_vox[q];
             o.len[r0 + head + q] = seg_len[q];
         }
+    } else if (MODE == MODE_SCATTER) {
+        scatter_segments(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
+                         (sr * G.ne + se) * G.na + sa, -tneg);
     } else {
         const int svox = (sr * G.ne + se) * G.na + sa;
         int64_t c_lo = 0, c_hi = o.n_chan;
@@ -1412,6 +1442,15 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
                 o.len[base + nseg] = len;
             } else if (MODE == MODE_INTEGRATE) {
                 acc += (double)o.density[c * o.chan_stride + vx] * len;
+            } else if (MODE == MODE_SCATTER) {   // (one walk: every channel per segment)
+                if (o.ray_chan_div > 0) {
+                    atomicAdd(o.acc + (ray / o.ray_chan_div) * o.chan_stride + vx,
+                              (double)o.density[ray] * len);
+                } else {
+                    for (int64_t ch = 0; ch < o.n_chan; ++ch)
+                        atomicAdd(o.acc + ch * o.chan_stride + vx,
+                                  (double)o.density[ch * o.out_chan_stride + ray] * len);
+                }
             }
             ++nseg;
         }
@@ -1482,6 +1521,8 @@ __device__ void exact_walk_wave(const GridDev& G, const TraceOut<T>& o, int64_t 
             o.vox[r0 + q] = seg_vox[q];
             o.len[r0 + q] = seg_len[q];
         }
+    } else if (MODE == MODE_SCATTER) {
+        scatter_segments(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
     } else {
         int64_t c_lo = 0, c_hi = o.n_chan;
         if (o.ray_chan_div > 0) {
@@ -2215,6 +2256,48 @@ extern "C" int sphrt_trace_integrate_f64(const sphrt_plan* plan, const sphrt_ray
                                          size_t workspace_size, void* stream) {
     return trace_integrate<double>(plan, rays, density, n_chan, chan_stride, ray_chan_div, out,
                                    out_chan_stride, workspace, workspace_size, stream);
+}
+
+extern "C" int sphrt_trace_backproject_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                           const double* y, int64_t n_chan, int64_t y_chan_stride,
+                                           int64_t ray_chan_div, double* acc, int64_t chan_stride,
+                                           void* workspace, size_t workspace_size, void* stream) {
+    // every refusal on the host, before the first HIP call (resolve asks for the stream's device)
+    if (!plan) return fail("null plan");
+    if (!rays) return fail("null ray batch");
+    if (!y || !acc) return fail("null back-projection argument (y or acc)");
+    if (n_chan < 1) return fail("n_chan must be >= 1");
+    if (ray_chan_div > 0 && n_chan != 1) return fail("ray_chan_div requires n_chan == 1");
+    if (rays->ndim < 0 || rays->ndim > kMaxDims)
+        return fail("ray batch rank %d out of range", rays->ndim);
+    int64_t n = 1;
+    for (int d = 0; d < rays->ndim; ++d) {
+        if (rays->shape[d] < 0) return fail("negative ray-batch extent");
+        n *= rays->shape[d];
+    }
+    const GridDev& P = plan->dev;
+    if (chan_stride < (int64_t)P.nr * P.ne * P.na)
+        return fail("chan_stride %lld is smaller than the grid's %lld voxels", (long long)chan_stride,
+                    (long long)P.nr * P.ne * P.na);
+    if (n_chan > 1 && y_chan_stride < n)
+        return fail("y_chan_stride %lld is smaller than the %lld rays", (long long)y_chan_stride,
+                    (long long)n);
+    if (n > 0 && (!workspace || workspace_size < workspace_bytes(P, n)))
+        return fail("trace workspace too small: %zu < %zu bytes", workspace_size,
+                    workspace_bytes(P, n));
+    GridDev G;
+    RaysDev R;
+    if (int e = resolve(plan, rays, G, R, stream)) return e;
+    DeviceGuard guard(plan->device);
+    TraceOut<double> o{};
+    o.density = y;
+    o.n_chan = n_chan;
+    o.chan_stride = chan_stride;
+    o.ray_chan_div = ray_chan_div;
+    o.out_chan_stride = y_chan_stride;
+    o.acc = acc;
+    return launch_trace<MODE_SCATTER, double>(G, R, o, workspace, workspace_size,
+                                              (hipStream_t)stream);
 }
 
 template <typename F>

@@ -909,7 +909,8 @@ def line_integrals(grid, geom, density):
     """No-store forward: trace and integrate in one fused pass, nothing persisted.
 
     Same result as ``Operator(grid, geom)(density)`` (not differentiable), without building the
-    segment CSR — the memory-capped / cold path (one kernel, O(output) memory)."""
+    segment CSR: one kernel, O(output) memory (``back_project`` is its adjoint and
+    ``MatrixFreeOperator`` the differentiable pair, built once)."""
     density = tr.as_tensor(density)
     dev = _lib.require_gpu(density.device)    # a GPU density computes where it lives
     with tr.cuda.device(dev):
@@ -927,6 +928,110 @@ def line_integrals(grid, geom, density):
                       div, _lib.ptr(out), n, _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
                    'sphrt_trace_integrate')
         return out.reshape(out_shape).to(device=density.device, dtype=density.dtype)
+
+
+# ----- matrix-free pair: the fused trace as forward (integrate) and adjoint (scatter) ------------
+
+def _adjoint_layout(grid, ray_shape, yshape):
+    """-> (n_chan, ray_chan_div, density shape) for line integrals of shape `yshape`: the rules
+    of _layout_for read backwards (host only).  Static grid: y (C..., *rays) -> (C..., nr, ne,
+    na).  Dynamic grid: y (T, ...) -> (T, nr, ne, na), as Operator.T(y, time_slices=True): view i
+    of a T-view collection into time slice i, a single detector's T images into the T slices."""
+    R = tuple(int(v) for v in ray_shape)
+    ys = tuple(int(v) for v in yshape)
+    if grid.dynamic:
+        if not ys:
+            raise ValueError('a dynamic grid expects line integrals with a leading time axis')
+        dshape = (ys[0],) + tuple(int(v) for v in grid.shape[1:])
+        if len(R) == 3 and R[0] not in (1, ys[0]) and ys[0] != 1:
+            raise ValueError(f'cannot pair {ys[0]} time steps with {R[0]} views')
+    else:
+        lead = ys[:len(ys) - len(R)]
+        if len(ys) < len(R) or ys[len(lead):] != R:
+            raise ValueError(f'line integrals of shape {ys} do not end with the ray shape {R}')
+        dshape = lead + tuple(int(v) for v in grid.shape)
+    n_chan, div, out_shape = _layout_for(grid, R, dshape)
+    if tuple(out_shape) != ys:
+        raise ValueError(f'line integrals of shape {ys} do not match the {tuple(out_shape)} '
+                         f'a density of shape {dshape} gives')
+    return n_chan, div, dshape
+
+
+def _fused_parts(grid, geom, dev):
+    """What a fused call needs: (plan, ray batch, trace workspace) on `dev`."""
+    plan = _Plan(grid, dev)
+    batch = _RayBatch(grid, geom.ray_starts, _geom_rays(geom, dev), dev)
+    return plan, batch, _workspace(_lib.load(), plan, batch.n, dev)
+
+
+def _fused_forward(parts, grid, density, dev):
+    """line_integrals over prebuilt parts (sphrt_trace_integrate_*)."""
+    plan, batch, ws = parts
+    n_chan, div, out_shape = _layout_for(grid, batch.shape, density.shape)
+    cdt = density.dtype if density.dtype in (tr.float32, tr.float64) else tr.float32
+    d = density.detach().to(device=dev, dtype=cdt).contiguous()
+    n = batch.n
+    out = tr.empty((n_chan, n) if div == 0 else (n,), dtype=cdt, device=dev)
+    lib = _lib.load()
+    fn = lib.sphrt_trace_integrate_f32 if cdt == tr.float32 else lib.sphrt_trace_integrate_f64
+    _lib.check(fn(plan.handle, batch.desc, _lib.ptr(d), n_chan, math.prod(grid.shape[-3:]), div,
+                  _lib.ptr(out), n, _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
+               'sphrt_trace_integrate')
+    return out.reshape(out_shape).to(device=density.device, dtype=density.dtype)
+
+
+def _fused_adjoint(parts, grid, y, dshape, rdtype, rdevice, dev):
+    """Back-projection of y into a `dshape` volume over prebuilt parts
+    (sphrt_trace_backproject_f64: the trace again, float64 atomics into a zeroed accumulator).
+    y goes in as float64 (from float32 for dtypes that are neither); the result is rounded to
+    `rdtype` (float32: sphrt_f64_to_f32) and left on `rdevice`."""
+    plan, batch, ws = parts
+    n_chan, div, _ = _layout_for(grid, batch.shape, dshape)
+    n = batch.n
+    ydt = y.dtype if y.dtype in (tr.float32, tr.float64) else tr.float32
+    yv = y.detach().to(device=dev, dtype=ydt).to(tr.float64).reshape(-1).contiguous()
+    if yv.numel() != n_chan * n:
+        raise ValueError(f'adjoint input has {yv.numel()} values, expected {n_chan * n}')
+    lib = _lib.load()
+    acc = tr.zeros(math.prod(dshape), dtype=tr.float64, device=dev)
+    _lib.check(lib.sphrt_trace_backproject_f64(
+        plan.handle, batch.desc, _lib.ptr(yv), n_chan, n, div, _lib.ptr(acc),
+        math.prod(grid.shape[-3:]), _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
+        'sphrt_trace_backproject_f64')
+    if rdtype == tr.float64:
+        res = acc
+    elif rdtype == tr.float32:
+        res = tr.empty(acc.shape, dtype=tr.float32, device=dev)
+        _lib.check(lib.sphrt_f64_to_f32(_lib.ptr(acc), _lib.ptr(res), acc.numel(),
+                                        _lib.stream_of(dev)), 'sphrt_f64_to_f32')
+    else:
+        res = acc.to(rdtype)
+    return res.reshape(dshape).to(rdevice)
+
+
+def _time_slices_rule(grid, time_slices):
+    """Operator.T's rule: a dynamic grid back-projects only on request (raytracer.py:733-734)."""
+    if grid.dynamic and not time_slices:
+        raise NotImplementedError
+
+
+def back_project(grid, geom, y, *, time_slices=None):
+    """No-store adjoint, the sibling of ``line_integrals``: trace and scatter in one fused pass,
+    nothing persisted.
+
+    Same result as ``Operator(grid, geom).T(y)`` with ``adjoint_mode='atomic'`` (float64 atomics:
+    within rounding of it, not bitwise reproducible) without building the segment CSR.  Static
+    grid: y (C..., *geom.shape) -> (C..., nr, ne, na).  Dynamic grid: y (T, ...) -> (T, nr, ne,
+    na) under the rules of ``Operator.T(y, time_slices=True)`` (time_slices=None takes them for a
+    dynamic grid; False raises as ``Operator.T`` does).  The result has y's dtype and device."""
+    y = tr.as_tensor(y)
+    _time_slices_rule(grid, grid.dynamic if time_slices is None else time_slices)
+    _, _, dshape = _adjoint_layout(grid, geom.shape, y.shape)    # (before any device is touched)
+    dev = _lib.require_gpu(y.device)    # a GPU y computes where it lives
+    with tr.cuda.device(dev):
+        parts = _fused_parts(grid, geom, dev)
+        _adjoint_layout(grid, parts[1].shape, y.shape)
+        return _fused_adjoint(parts, grid, y, dshape, y.dtype, y.device, dev)
 
 
 # switches of the Python construction sequence: any of them set keeps Operator construction in
@@ -1886,3 +1991,81 @@ class Operator:
 
     def plot(self, *args, **kwargs):
         raise NotImplementedError('plotting is out of scope for sph_raytracer_amd')
+
+
+# ----- the matrix-free operator -----------------------------------------------------------------
+
+class _MatrixFreeIntegral(_LineIntegral):
+    """y = A x with dA/dx = A^T, both by the fused trace: nothing is stored between them."""
+
+
+class MatrixFreeOperator:
+    """``Operator`` without the stored trace: every forward traces and integrates
+    (``line_integrals``), every adjoint traces and scatters (``back_project``), and only what
+    those build per call is kept — the plan's boundary tables, the ray batch and the trace
+    workspace, O(rays) memory with nothing per segment.  For problems whose segment CSR does not
+    fit; an ``Operator`` is several times faster per call once it is built.
+
+    Args:
+        grid, geom, dynamic, device: as for ``Operator`` (results of ``T`` live on `device`;
+        compute runs on the GPU it names, else the current one).  ftype=float32 and invalid=True
+        (the reference-mode traces) are not available here: use ``Operator``.
+    ``op(density)`` equals ``line_integrals`` and is differentiable; ``op.T(y)`` follows
+    ``Operator.T`` (and also takes leading channel axes on a static grid).  The adjoint sums
+    with float64 atomics: within rounding of ``Operator.T``, not bitwise reproducible.  There are
+    no ``regs`` / ``lens`` / ``segments`` views: nothing is stored to show.  The workspace is
+    shared by the calls: use an operator from one stream at a time."""
+
+    def __init__(self, grid, geom, dynamic=False, ftype=FTYPE, device=DEVICE, invalid=False):
+        if ftype != tr.float64 or invalid:
+            raise NotImplementedError('MatrixFreeOperator traces in float64 with masking only; '
+                                      'ftype=float32 and invalid=True need Operator')
+        self.grid = grid
+        self.geom = geom
+        if dynamic is None:
+            dynamic = isinstance(geom, ViewGeomCollection)
+        self.dynamic = dynamic
+        self.device = device
+        dev = _lib.require_gpu(device)
+        self._cdev = dev
+        self._rdev = dev if tr.device(device).type == 'cuda' else tr.device(device)
+        with tr.cuda.device(dev):
+            self._parts = _fused_parts(grid, geom, dev)
+        self._ray_shape = self._parts[1].shape
+
+    def _layout(self, shape):
+        """-> (n_chan, ray_chan_div, out_shape) for a density of `shape`."""
+        return _layout_for(self.grid, self._ray_shape, shape)
+
+    def __call__(self, density):
+        """Line integrals of ``density`` along every ray (``Operator.__call__``'s shapes).
+        Differentiable in ``density``."""
+        density = tr.as_tensor(density)
+        if density.requires_grad and tr.is_grad_enabled():
+            return _MatrixFreeIntegral.apply(density, self)
+        return self._apply_forward(density)
+
+    def _apply_forward(self, density):
+        with tr.cuda.device(self._cdev):
+            return _fused_forward(self._parts, self.grid, density, self._cdev)
+
+    def _apply_adjoint(self, y, dshape, ddtype, ddevice):
+        with tr.cuda.device(self._cdev):
+            return _fused_adjoint(self._parts, self.grid, y, tuple(dshape), ddtype, ddevice,
+                                  self._cdev)
+
+    def T(self, line_integrations, *, time_slices=False):
+        """Back-projection of ``line_integrations`` into a grid.shape volume, as ``Operator.T``:
+        static grids (leading channel axes kept), or with ``time_slices=True`` a dynamic grid's
+        (T, ...) images into (T, nr, ne, na); a dynamic grid without it raises
+        NotImplementedError."""
+        y = tr.as_tensor(line_integrations)
+        _time_slices_rule(self.grid, time_slices)
+        _, _, dshape = _adjoint_layout(self.grid, self._ray_shape, y.shape)
+        return self._apply_adjoint(y, dshape, y.dtype, self._rdev)
+
+    def __repr__(self):
+        if self.dynamic:
+            return (f"MatrixFreeOperator({(self.geom.shape[0], *self.grid.shape)} → "
+                    f"{self.geom.shape})")
+        return f"MatrixFreeOperator({self.grid.shape} → {self.geom.shape})"
