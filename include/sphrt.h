@@ -495,6 +495,26 @@ int sphrt_trace_backproject_f64(const sphrt_plan *plan, const sphrt_rays *rays, 
                                 int64_t n_chan, int64_t y_chan_stride, int64_t ray_chan_div,
                                 double *acc, int64_t chan_stride,
                                 void *workspace, size_t workspace_size, void *stream);
+/* fused no-store least-squares gradient: one trace that integrates, forms the residual and
+ * scatters it, nothing persisted.  For ray i and channel c (channels and time slices as
+ * sphrt_trace_integrate_f64: density and acc channels chan_stride apart, m and yhat channels
+ * y_chan_stride apart; with ray_chan_div > 0, n_chan == 1 and ray i reads and updates slice
+ * i / ray_chan_div):
+ *   yhat[c][i] = sum density[c][vox] * len        bitwise what sphrt_trace_integrate_f64 writes
+ *   r          = (yhat[c][i] - m[c][i]) * scale   two roundings, as sphrt_sq_residual_f64
+ *   acc[c][vox] += r * len                        for every segment of ray i (float64 atomics)
+ * so acc receives A^T(scale * (A density - m)) and yhat A density.  acc is zeroed and owned by the
+ * caller (sums are not bitwise reproducible); rays that miss the grid write yhat = 0 and add
+ * nothing.  Fails on the host, before any launch, on a null plan or ray batch, a null density, m,
+ * yhat or acc, n_chan < 1, ray_chan_div > 0 with n_chan != 1, a chan_stride below the grid's
+ * voxel count, a y_chan_stride below the ray count when n_chan > 1, and a workspace smaller than
+ * sphrt_trace_workspace_bytes.  Replaces Operator.__call__ plus Operator.T of the residual
+ * (raytracer.py:692-748) over a trace that is never stored. */
+int sphrt_trace_normal_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                           const double *density, const double *m, double scale,
+                           int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+                           double *yhat, int64_t y_chan_stride,
+                           double *acc, void *workspace, size_t workspace_size, void *stream);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,9 @@ _SIGNATURES = [
                                           c_i64, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
     ('sphrt_trace_backproject_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_i64, c_i64,
                                             c_i64, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
+    ('sphrt_trace_normal_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_dbl,
+                                       c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                       ctypes.c_size_t, c_vp]),
 ]
 EXPORTED = [s[0] for s in _SIGNATURES]
 TRACE_F32, TRACE_INVALID, TRACE_FRESH_RAYS = 1, 2, 4   # sphrt_trace_reference flags (sphrt.h)

@@ -15,8 +15,9 @@
 //      for lists of <= 512 entries), differenced and the non-zero in-grid segments compacted, in
 //      order, back into LDS;
 //   4. depending on MODE the segments are counted, copied to the CSR, integrated against the
-//      density right away (no-store forward), or scattered into a float64 accumulator weighted
-//      by the ray's value (no-store adjoint).
+//      density right away (no-store forward), scattered into a float64 accumulator weighted
+//      by the ray's value (no-store adjoint), or both from the one list (the least-squares
+//      gradient: integrate, subtract the measurement, scatter the residual).
 // Nothing of size K ever reaches HBM.
 //
 // Exact ties.  The reference orders equal distances the way libstdc++'s introsort happens to
@@ -39,9 +40,11 @@ namespace sphrt {
 // one pass that writes each ray's segments into its bounded slot of a staging CSR (compacted
 // afterwards).  INTEGRATE: the no-store forward.  SCATTER: the no-store adjoint — the same trace
 // with the last step reversed, acc[vox] += y[ray] * len in float64 atomics instead of
-// out[ray] = sum rho[vox] * len.
+// out[ray] = sum rho[vox] * len.  NORMAL: both on one trace, the gradient of a squared residual
+// (the normal equations' A^T(s (A x - m))) — INTEGRATE's sum, written to out, then
+// acc[vox] += ((out[ray] - m[ray]) * scale) * len over the same segments.
 enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4,
-       MODE_SCATTER = 5 };
+       MODE_SCATTER = 5, MODE_NORMAL = 6 };
 constexpr int kNone = 0x7fffffff;  // "no update" in the forward-fill scans
 constexpr int kWavesPerBlock = 4;
 
@@ -427,6 +430,8 @@ struct TraceOut {
     unsigned long long* n_over;      // EMIT: rays whose segments exceed their bound
     unsigned long long* n_heap;      // workspace: depth-limit ranges, rank-sorted / heap-sorted
     int wedge;                       // solve only the half-planes of a line's azimuth wedge
+    const double* meas;       // NORMAL: the measurements, laid out as out (out_chan_stride apart)
+    double scale;             // NORMAL: the residual's factor
 };
 
 // EMIT: ray `ray` has `cnt` segments; its staging slot is [row_ptr[ray], row_ptr[ray + 1]) (the
@@ -466,6 +471,36 @@ __device__ __forceinline__ void scatter_segments(const TraceOut<T>& o, int64_t r
         double* acc = o.acc + c * o.chan_stride;
         if (head && lane == 0) atomicAdd(acc + hvox, yv * hlen);
         for (int q = lane; q < nseg; q += 64) atomicAdd(acc + seg_vox[q], yv * seg_len[q]);
+    }
+}
+
+// NORMAL: the same list integrated and scattered by the whole wave, channel by channel (the
+// channels of INTEGRATE).  The sum is MODE_INTEGRATE's — head segment on lane 0, strided lanes,
+// wave_sum, the same products in the same order — and goes to out; every lane then holds it and
+// forms the residual r = (sum - m) * scale (two roundings, sphrt_sq_residual_f64's), which is
+// scattered as SCATTER scatters y.
+template <typename T>
+__device__ __forceinline__ void normal_segments(const TraceOut<T>& o, int64_t ray, int lane,
+                                                int nseg, const int32_t* seg_vox,
+                                                const double* seg_len, bool head, int hvox,
+                                                double hlen) {
+    int64_t c_lo = 0, c_hi = o.n_chan;
+    if (o.ray_chan_div > 0) {
+        c_lo = ray / o.ray_chan_div;
+        c_hi = c_lo + 1;
+    }
+    for (int64_t c = c_lo; c < c_hi; ++c) {
+        const T* rho = o.density + c * o.chan_stride;
+        double sum = 0.0;
+        if (head && lane == 0) sum = (double)rho[hvox] * hlen;
+        for (int q = lane; q < nseg; q += 64) sum += (double)rho[seg_vox[q]] * seg_len[q];
+        sum = wave_sum(sum);
+        const int64_t oc = (o.ray_chan_div > 0) ? 0 : c;
+        if (lane == 0) o.out[oc * o.out_chan_stride + ray] = (T)sum;
+        const double r = (sum - o.meas[oc * o.out_chan_stride + ray]) * o.scale;
+        double* acc = o.acc + c * o.chan_stride;
+        if (head && lane == 0) atomicAdd(acc + hvox, r * hlen);
+        for (int q = lane; q < nseg; q += 64) atomicAdd(acc + seg_vox[q], r * seg_len[q]);
     }
 }
 
@@ -1040,6 +1075,9 @@ __device__ void trace_one(const GridDev& G, const RayGeo& g, const double t1c_o,
     } else if (MODE == MODE_SCATTER) {
         scatter_segments(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
                          (sr * G.ne + se) * G.na + sa, -tneg);
+    } else if (MODE == MODE_NORMAL) {
+        normal_segments(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
+                        (sr * G.ne + se) * G.na + sa, -tneg);
     } else {
         const int svox = (sr * G.ne + se) * G.na + sa;
         int64_t c_lo = 0, c_hi = o.n_chan;
@@ -1217,7 +1255,7 @@ __global__ __launch_bounds__(256) void screen_kernel(GridDev G, RaysDev R, Trace
                             : 0;
     if (active && !hit) {
         if (MODE == MODE_COUNT) o.counts[ray] = 0;
-        if (MODE == MODE_INTEGRATE) {
+        if (MODE == MODE_INTEGRATE || MODE == MODE_NORMAL) {
             const int64_t nc = o.ray_chan_div > 0 ? 1 : o.n_chan;
             for (int64_t c = 0; c < nc; ++c) o.out[c * o.out_chan_stride + ray] = (T)0;
         }
@@ -1408,13 +1446,18 @@ template <int MODE, typename T, typename F, bool INV, class V>
 __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, const int* s,
                            const V& v) {
     const int K = G.K, r_lim = 2 * G.nbr, e_lim = 2 * G.nbr + 2 * G.nbe;
+    // NORMAL: INTEGRATE's walks (one per channel, each writing out), then one more (scat) that
+    // scatters the residuals of what this lane just wrote
+    constexpr bool kSum = MODE == MODE_INTEGRATE || MODE == MODE_NORMAL;
     int64_t c_lo = 0, c_hi = o.n_chan;
-    if (MODE == MODE_INTEGRATE && o.ray_chan_div > 0) {
+    if (kSum && o.ray_chan_div > 0) {
         c_lo = ray / o.ray_chan_div;
         c_hi = c_lo + 1;
     }
-    if (MODE != MODE_INTEGRATE) c_hi = c_lo + 1;
-    for (int64_t c = c_lo; c < c_hi; ++c) {
+    if (!kSum) c_hi = c_lo + 1;
+    const int64_t c_end = MODE == MODE_NORMAL ? c_hi + 1 : c_hi;
+    for (int64_t c = c_lo; c < c_end; ++c) {
+        const bool scat = MODE == MODE_NORMAL && c == c_hi;
         int cr = s[0], ce = s[1], ca = s[2];
         int64_t nseg = 0;
         double acc = 0.0;
@@ -1440,8 +1483,14 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
             if (MODE == MODE_FILL || (MODE == MODE_EMIT && nseg < cap)) {
                 o.vox[base + nseg] = vx;
                 o.len[base + nseg] = len;
-            } else if (MODE == MODE_INTEGRATE) {
+            } else if (kSum && !scat) {
                 acc += (double)o.density[c * o.chan_stride + vx] * len;
+            } else if (MODE == MODE_NORMAL) {
+                for (int64_t ch = c_lo; ch < c_hi; ++ch) {
+                    const int64_t oc = (o.ray_chan_div > 0 ? 0 : ch) * o.out_chan_stride + ray;
+                    const double r = ((double)o.out[oc] - o.meas[oc]) * o.scale;
+                    atomicAdd(o.acc + ch * o.chan_stride + vx, r * len);
+                }
             } else if (MODE == MODE_SCATTER) {   // (one walk: every channel per segment)
                 if (o.ray_chan_div > 0) {
                     atomicAdd(o.acc + (ray / o.ray_chan_div) * o.chan_stride + vx,
@@ -1456,7 +1505,7 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
         }
         if (MODE == MODE_COUNT) o.counts[ray] = (int32_t)nseg;
         if (MODE == MODE_EMIT) (void)emit_slot(o, ray, nseg, true);
-        if (MODE == MODE_INTEGRATE) {
+        if (kSum && !scat) {
             const int64_t oc = o.ray_chan_div > 0 ? 0 : c;
             o.out[oc * o.out_chan_stride + ray] = (T)acc;
         }
@@ -1523,6 +1572,8 @@ __device__ void exact_walk_wave(const GridDev& G, const TraceOut<T>& o, int64_t 
         }
     } else if (MODE == MODE_SCATTER) {
         scatter_segments(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
+    } else if (MODE == MODE_NORMAL) {
+        normal_segments(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
     } else {
         int64_t c_lo = 0, c_hi = o.n_chan;
         if (o.ray_chan_div > 0) {
@@ -2258,14 +2309,15 @@ extern "C" int sphrt_trace_integrate_f64(const sphrt_plan* plan, const sphrt_ray
                                    out_chan_stride, workspace, workspace_size, stream);
 }
 
-extern "C" int sphrt_trace_backproject_f64(const sphrt_plan* plan, const sphrt_rays* rays,
-                                           const double* y, int64_t n_chan, int64_t y_chan_stride,
-                                           int64_t ray_chan_div, double* acc, int64_t chan_stride,
-                                           void* workspace, size_t workspace_size, void* stream) {
-    // every refusal on the host, before the first HIP call (resolve asks for the stream's device)
+// The refusals the fused entries with an accumulator share (back-projection, normal), every one
+// on the host, before the first HIP call (resolve asks for the stream's device).  null_arg: the
+// entry's own message when one of its buffers is null.
+static int refuse_fused(const sphrt_plan* plan, const sphrt_rays* rays, const char* null_arg,
+                        int64_t n_chan, int64_t y_chan_stride, int64_t ray_chan_div,
+                        int64_t chan_stride, void* workspace, size_t workspace_size) {
     if (!plan) return fail("null plan");
     if (!rays) return fail("null ray batch");
-    if (!y || !acc) return fail("null back-projection argument (y or acc)");
+    if (null_arg) return fail("%s", null_arg);
     if (n_chan < 1) return fail("n_chan must be >= 1");
     if (ray_chan_div > 0 && n_chan != 1) return fail("ray_chan_div requires n_chan == 1");
     if (rays->ndim < 0 || rays->ndim > kMaxDims)
@@ -2285,6 +2337,18 @@ extern "C" int sphrt_trace_backproject_f64(const sphrt_plan* plan, const sphrt_r
     if (n > 0 && (!workspace || workspace_size < workspace_bytes(P, n)))
         return fail("trace workspace too small: %zu < %zu bytes", workspace_size,
                     workspace_bytes(P, n));
+    return 0;
+}
+
+extern "C" int sphrt_trace_backproject_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                           const double* y, int64_t n_chan, int64_t y_chan_stride,
+                                           int64_t ray_chan_div, double* acc, int64_t chan_stride,
+                                           void* workspace, size_t workspace_size, void* stream) {
+    if (int e = refuse_fused(plan, rays,
+                             !y || !acc ? "null back-projection argument (y or acc)" : nullptr,
+                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
+                             workspace_size))
+        return e;
     GridDev G;
     RaysDev R;
     if (int e = resolve(plan, rays, G, R, stream)) return e;
@@ -2298,6 +2362,35 @@ extern "C" int sphrt_trace_backproject_f64(const sphrt_plan* plan, const sphrt_r
     o.acc = acc;
     return launch_trace<MODE_SCATTER, double>(G, R, o, workspace, workspace_size,
                                               (hipStream_t)stream);
+}
+
+extern "C" int sphrt_trace_normal_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                      const double* density, const double* m, double scale,
+                                      int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+                                      double* yhat, int64_t y_chan_stride, double* acc,
+                                      void* workspace, size_t workspace_size, void* stream) {
+    if (int e = refuse_fused(plan, rays,
+                             !density || !m || !yhat || !acc
+                                 ? "null normal argument (density, m, yhat or acc)" : nullptr,
+                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
+                             workspace_size))
+        return e;
+    GridDev G;
+    RaysDev R;
+    if (int e = resolve(plan, rays, G, R, stream)) return e;
+    DeviceGuard guard(plan->device);
+    TraceOut<double> o{};
+    o.density = density;
+    o.n_chan = n_chan;
+    o.chan_stride = chan_stride;
+    o.ray_chan_div = ray_chan_div;
+    o.out = yhat;
+    o.out_chan_stride = y_chan_stride;
+    o.acc = acc;
+    o.meas = m;
+    o.scale = scale;
+    return launch_trace<MODE_NORMAL, double>(G, R, o, workspace, workspace_size,
+                                             (hipStream_t)stream);
 }
 
 template <typename F>

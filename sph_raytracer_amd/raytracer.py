@@ -998,15 +998,60 @@ def _fused_adjoint(parts, grid, y, dshape, rdtype, rdevice, dev):
         plan.handle, batch.desc, _lib.ptr(yv), n_chan, n, div, _lib.ptr(acc),
         math.prod(grid.shape[-3:]), _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
         'sphrt_trace_backproject_f64')
+    return _from_f64(acc, rdtype, dev).reshape(dshape).to(rdevice)
+
+
+def _from_f64(a, rdtype, dev):
+    """A fused call's float64 result rounded to `rdtype` (float32: sphrt_f64_to_f32)."""
     if rdtype == tr.float64:
-        res = acc
-    elif rdtype == tr.float32:
-        res = tr.empty(acc.shape, dtype=tr.float32, device=dev)
-        _lib.check(lib.sphrt_f64_to_f32(_lib.ptr(acc), _lib.ptr(res), acc.numel(),
-                                        _lib.stream_of(dev)), 'sphrt_f64_to_f32')
-    else:
-        res = acc.to(rdtype)
-    return res.reshape(dshape).to(rdevice)
+        return a
+    if rdtype != tr.float32:
+        return a.to(rdtype)
+    res = tr.empty(a.shape, dtype=tr.float32, device=dev)
+    _lib.check(_lib.load().sphrt_f64_to_f32(_lib.ptr(a), _lib.ptr(res), a.numel(),
+                                            _lib.stream_of(dev)), 'sphrt_f64_to_f32')
+    return res
+
+
+def _to_f64(a, dev):
+    """A fused call's float64 input: float32 and float64 promoted exactly, any other dtype from
+    float32 (as _fused_adjoint takes y)."""
+    dt = a.dtype if a.dtype in (tr.float32, tr.float64) else tr.float32
+    return a.detach().to(device=dev, dtype=dt).to(tr.float64).reshape(-1).contiguous()
+
+
+def _gradient_layout(grid, ray_shape, dshape, mshape):
+    """-> (n_chan, ray_chan_div, output shape) for measurements of shape `mshape`, which must be
+    line integrals of these rays (_adjoint_layout: its errors, an unpairable T among them), and a
+    density of shape `dshape`, which must be the one they are the output of (host only)."""
+    n_chan, div, want = _adjoint_layout(grid, ray_shape, mshape)
+    if tuple(int(v) for v in dshape) != tuple(want):
+        raise ValueError(f'density of shape {tuple(dshape)} does not match the {tuple(want)} '
+                         f'that measurements of shape {tuple(mshape)} are line integrals of')
+    return n_chan, div, tuple(int(v) for v in mshape)
+
+
+def _launch_normal(parts, grid, d, m, scale, n_chan, div, yhat, acc, dev):
+    """sphrt_trace_normal_f64 over prebuilt parts: flat float64 d and m on `dev`; yhat receives
+    A d, the zeroed acc gains A^T(scale (A d - m))."""
+    plan, batch, ws = parts
+    _lib.check(_lib.load().sphrt_trace_normal_f64(
+        plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), scale, n_chan,
+        math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(acc), _lib.ptr(ws),
+        ws.numel(), _lib.stream_of(dev)), 'sphrt_trace_normal_f64')
+
+
+def _fused_gradient(parts, grid, density, m, scale, dev):
+    """(A density, A^T(scale (A density - m))) from one trace over prebuilt parts, computed in
+    float64 and returned in density's dtype on density's device."""
+    n_chan, div, out_shape = _gradient_layout(grid, parts[1].shape, density.shape, m.shape)
+    d, mv = _to_f64(density, dev), _to_f64(m, dev)
+    yhat = tr.empty(mv.numel(), dtype=tr.float64, device=dev)
+    acc = tr.zeros(d.numel(), dtype=tr.float64, device=dev)
+    _launch_normal(parts, grid, d, mv, float(scale), n_chan, div, yhat, acc, dev)
+    rdt, rdev = density.dtype, density.device
+    return (_from_f64(yhat, rdt, dev).reshape(out_shape).to(rdev),
+            _from_f64(acc, rdt, dev).reshape(density.shape).to(rdev))
 
 
 def _time_slices_rule(grid, time_slices):
@@ -2012,7 +2057,9 @@ class MatrixFreeOperator:
         (the reference-mode traces) are not available here: use ``Operator``.
     ``op(density)`` equals ``line_integrals`` and is differentiable; ``op.T(y)`` follows
     ``Operator.T`` (and also takes leading channel axes on a static grid).  The adjoint sums
-    with float64 atomics: within rounding of ``Operator.T``, not bitwise reproducible.  There are
+    with float64 atomics: within rounding of ``Operator.T``, not bitwise reproducible.
+    ``op.residual_gradient(density, m, scale)`` gives ``op(density)`` and
+    ``op.T(scale * (op(density) - m))`` from one trace instead of two.  There are
     no ``regs`` / ``lens`` / ``segments`` views: nothing is stored to show.  The workspace is
     shared by the calls: use an operator from one stream at a time."""
 
@@ -2063,6 +2110,28 @@ class MatrixFreeOperator:
         _time_slices_rule(self.grid, time_slices)
         _, _, dshape = _adjoint_layout(self.grid, self._ray_shape, y.shape)
         return self._apply_adjoint(y, dshape, y.dtype, self._rdev)
+
+    def residual_gradient(self, density, measurements, scale=1.0):
+        """-> (yhat, grad) from one trace (sphrt_trace_normal_f64): ``yhat = op(density)`` and
+        ``grad = A^T(scale * (yhat - measurements))``, the gradient in ``density`` of
+        ``0.5 * scale * ((op(density) - measurements) ** 2).sum()`` — what ``op`` followed by
+        ``op.T`` of the residual gives, without tracing the rays a second time.
+
+        ``measurements`` has ``op(density)``'s shape.  Static grids take leading channel axes; a
+        dynamic grid pairs time slices with views as the forward does, so ``grad`` is autograd's
+        gradient of the dynamic forward.  Computed in float64 (``yhat`` is bitwise the float64
+        forward; ``grad`` sums with float64 atomics) and returned in ``density``'s dtype on its
+        device.  Not differentiable."""
+        density, m = tr.as_tensor(density), tr.as_tensor(measurements)
+        _gradient_layout(self.grid, self._ray_shape, density.shape, m.shape)   # (host only)
+        with tr.cuda.device(self._cdev):
+            return _fused_gradient(self._parts, self.grid, density, m, scale, self._cdev)
+
+    def _normal_into(self, d, m, scale, yhat, acc):
+        """residual_gradient for gd's fused loop (retrieval._gd_direct): a grid.shape float64
+        density and flat float64 measurements on the compute device, into the caller's yhat and
+        zeroed acc; nothing allocated."""
+        _launch_normal(self._parts, self.grid, d, m, scale, 1, 0, yhat, acc, self._cdev)
 
     def __repr__(self):
         if self.dynamic:

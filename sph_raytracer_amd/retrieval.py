@@ -62,6 +62,8 @@ def gd(f, y, model, coeffs=None, num_iterations=100, loss_fns=[SquareLoss()], op
     # implementation choice (foreach on GPU tensors) unless the caller passes foreach=/fused=
     opt = optim(optim_vars, **kwargs)
     plan = _direct_plan(f, y, model, coeffs, loss_fns, optim_vars)
+    if plan is None:
+        plan = _fused_plan(f, y, model, coeffs, loss_fns, optim_vars)
     if plan is not None:
         return _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar)
     losses = {fn: [] for fn in loss_fns}
@@ -128,6 +130,22 @@ def _direct_plan(f, y, model, coeffs, loss_fns, optim_vars):
     from .raytracer import Operator
     if not isinstance(f, Operator) or f.dynamic or f._csr is None or y is None:
         return None
+    return _loop_terms(f, y, model, coeffs, loss_fns, optim_vars)
+
+
+def _fused_plan(f, y, model, coeffs, loss_fns, optim_vars):
+    """`_direct_plan` for a MatrixFreeOperator on a static grid: the same loop and the same
+    conditions, with the forward and the adjoint of an iteration in one trace
+    (MatrixFreeOperator.residual_gradient's kernel).  Anything else takes the autograd loop."""
+    from .raytracer import MatrixFreeOperator
+    if not isinstance(f, MatrixFreeOperator) or f.dynamic or f.grid.dynamic or y is None:
+        return None
+    return _loop_terms(f, y, model, coeffs, loss_fns, optim_vars)
+
+
+def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
+    """(SquareLoss, NegRegularizer or None) when model, variables, measurements and loss terms
+    are those `_gd_direct` runs over the operator `f`, else None."""
     if type(model) is not FullyDenseModel or hasattr(model, 'proj'):
         return None
     if len(optim_vars) != 1 or optim_vars[0] is not coeffs or coeffs.dtype != t.float64:
@@ -160,9 +178,11 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     iterates are the same (the Operator forward, the adjoint of the SquareLoss residual, the
     NegRegularizer's -lam/N on negative voxels, the optimiser step), without building and walking
     a graph every iteration: one forward, one adjoint, the residual kernel of csrc/loss.hip
-    and the optimiser step (for Adam, one csrc/loss.hip launch that also applies the
-    regulariser and keeps the forward's brick-staged density current; otherwise the
-    regulariser's own kernel, then opt.step()).  The loss values are the fused kernels' partial
+    (over a MatrixFreeOperator, `_fused_plan`: one trace that integrates, forms the scaled
+    residual and scatters it — sphrt_trace_normal_f64 — and the residual kernel for the loss's
+    partial sums only, on the forward that trace wrote) and the optimiser step (for Adam, one
+    csrc/loss.hip launch that also applies the regulariser and keeps the forward's brick-staged
+    density current; otherwise the regulariser's own kernel, then opt.step()).  The loss values are the fused kernels' partial
     sums, summed for all iterations after the loop: deterministic, within rounding of the
     autograd loop's torch.mean.
 
@@ -178,6 +198,8 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     before the regulariser and the optimiser step (which are then identical on every rank) and
     to the SquareLoss sums after the loop."""
     from . import _lib
+    from .raytracer import MatrixFreeOperator
+    fused = isinstance(f, MatrixFreeOperator)
     sq, neg = plan
     losses = {fn: [] for fn in loss_fns}
     y.requires_grad_()                 # (the reference's own side effect on y)
@@ -195,10 +217,10 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     lib = _lib.load()
     n_meas, n_vox = yd.numel(), coeffs.numel()
     # Adam keeps the forward's brick-staged density current (no pack launch per iteration)
-    staged = f._stage_for_loop(coeffs.dtype) if step is not None else None
+    staged = f._stage_for_loop(coeffs.dtype) if step is not None and not fused else None
     if staged is not None and f._csr['n'] != n_meas:
         staged = None
-    order = f._adjoint_trace_order()
+    order = f._adjoint_trace_order() if not fused else None
     if order is not None and order.numel() != n_meas:
         order = None
     # the loop's own forward descriptor (a copy of the trace's): the staged one above, and with a
@@ -214,7 +236,9 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
             loop_desc = sd
             y_res, res_order = yd.reshape(-1).index_select(0, f._ray_id_long()), None
     yhat_buf = t.empty(n_meas, dtype=coeffs.dtype, device=coeffs.device) \
-        if loop_desc is not None else None
+        if loop_desc is not None or fused else None
+    # the fused trace subtracts float64 measurements (a float32 y promoted once, exactly)
+    m64 = yd.to(t.float64).reshape(-1) if fused else None
     # every iteration's loss as the workgroup partial sums of its fused kernel, one row per
     # iteration, summed once after the loop (no reduction launch, no host sync per iteration)
     ps, pn = lib.sphrt_loss_partials(n_meas), lib.sphrt_loss_partials(n_vox)
@@ -236,7 +260,13 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 opt.zero_grad()
                 d = coeffs.detach()
                 stream = _lib.stream_of(d.device)
-                if loop_desc is not None:
+                if fused:
+                    # f(d) into yhat_buf and A^T((f(d) - y) * (2 lam / N)) into a zeroed g from
+                    # one trace; the residual launch below then only sums the loss
+                    g = t.zeros_like(d)
+                    f._normal_into(d, m64, 2 * c_sq, yhat_buf, g)
+                    yhat = yhat_buf.view(yd.shape)
+                elif loop_desc is not None:
                     # (staged: the forward reads the brick copy the previous Adam launch wrote;
                     # the first one packs it)
                     f._forward_staged(d, yhat_buf, loop_desc)
@@ -256,8 +286,9 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                     _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
                     2 * c_sq, _lib.ptr(res_order), _lib.ptr(r_scaled), _lib.ptr(part_sq[it]),
                     stream), 'sphrt_sq_residual_f64')
-                g = f._apply_adjoint(r_scaled, tuple(d.shape), d.dtype, d.device,
-                                     trace_order=order is not None)
+                if not fused:
+                    g = f._apply_adjoint(r_scaled, tuple(d.shape), d.dtype, d.device,
+                                         trace_order=order is not None)
                 if reduce is not None:
                     reduce(g)          # data-parallel: the sum of every rank's adjoint
                 if step is not None:
