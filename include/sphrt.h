@@ -516,6 +516,80 @@ int sphrt_trace_normal_f64(const sphrt_plan *plan, const sphrt_rays *rays,
                            double *yhat, int64_t y_chan_stride,
                            double *acc, void *workspace, size_t workspace_size, void *stream);
 
+/* ---- deterministic no-store adjoint: fixed-point scatter (csrc/fixed.hpp) --------------------
+ * The two entries above sum y * len with float64 atomics, so their results differ in the last
+ * bits from run to run.  The entries below quantise every term onto one power-of-two grid and
+ * add it with integer atomics: integer addition is associative, so the result is bitwise
+ * independent of the ray order, the workgroup schedule and the way a batch is split over calls.
+ * The contract, exact on host and device:
+ *   exponent  from a bound B >= |term| of every term (finite, > 0): frexp(B) = f * 2^E with f in
+ *             [0.5, 1); the quantum is q = 2^(E - 61) (B is a rounded product: one bit of margin
+ *             below int64's 63).
+ *   quantise  k = llrint(ldexp(term, 61 - E)), round half to even; |k| <= 2^61.
+ *   split     carry-save, no carry detection: element j of the accumulator owns the two adjacent
+ *             int64 acc[2j] = lo and acc[2j + 1] = hi; lo += k & 0xffffffff, hi += k >> 32
+ *             (arithmetic shift); its integer is V = hi * 2^32 + lo.  Both are plain integer
+ *             sums, so accumulators filled under one record may be summed elementwise.
+ *             Capacity: fewer than 2^31 adds per element over an accumulator's lifetime.
+ *   value     ldexp(D, E - 61), D = V converted to double correctly rounded, ties to even.
+ *   record    16 bytes of device memory, {int32 E, int32 flags, 8 bytes pad}.  flags bit 0: the
+ *             bound was zero — nothing is added, every value is +0.0.  flags bit 1: the bound was
+ *             not finite — nothing is added and EVERY value is NaN (the float64-atomic entries
+ *             poison only the voxels the inf or NaN reaches; this way no host sync is needed).
+ *
+ * sphrt_fixed_scale_f64 (no counterpart above: the float64 sums need no scale) writes the record
+ * of B = fa * max|a_i| + fb * max|b_j| (b NULL: the first term only), stream-ordered, no host
+ * sync.  The maxima are taken over the bit patterns of |x| (a NaN sorts above infinity: the bound
+ * is then not finite).  While it runs, the record's own 16 bytes hold the two maxima; the entry
+ * resets them itself, the caller zeroes nothing.  For sphrt_trace_backproject_fixed_f64: a = y,
+ * fa = L with L = 2 * r_b[nr], the outer sphere's diameter: no segment between two crossings of
+ * a unit direction is longer.  (One kind is: the head segment of a start inside the grid runs
+ * back to the farthest crossing behind the start, and directions shorter than 1 stretch every
+ * length.  Terms above the bound are still quantised and added exactly, up to 2^32 times the
+ * bound; each takes that many times more of the capacity, which is a bound on the sum of
+ * |hi|: 2^63.)  For
+ * sphrt_trace_normal_fixed_f64: a = density, fa = |scale| * L * L, b = m, fb = |scale| * L
+ * (|yhat| <= max|density| * L).  Fails on the host on a null record, a negative length, a null
+ * input of non-zero length and a negative or NaN factor. */
+int sphrt_fixed_scale_f64(const double *a, int64_t na, double fa,
+                          const double *b, int64_t nb, double fb,
+                          void *scale_rec, void *stream);
+/* Replaces sphrt_trace_backproject_f64 where the result must be reproducible: the same trace and
+ * the same products y * len (one rounding each), then quantised under *scale_rec and added as two
+ * 64-bit integer atomics.  acc holds 2 * n_chan * chan_stride int64 ({lo, hi} of element
+ * c * chan_stride + vox), zeroed and owned by the caller; several calls may add into one acc
+ * under one record (a batch split over calls gives the same bits as the whole).  Two integer
+ * atomics per segment instead of one float64 atomic, 16 bytes per element instead of 8.  Fails on
+ * the host, before any launch, as sphrt_trace_backproject_f64 does, and on a null scale record
+ * and on n_rays * max(n_chan, 1) >= 2^29 (the capacity above). */
+int sphrt_trace_backproject_fixed_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                                      const double *y, int64_t n_chan, int64_t y_chan_stride,
+                                      int64_t ray_chan_div, int64_t *acc, int64_t chan_stride,
+                                      const void *scale_rec,
+                                      void *workspace, size_t workspace_size, void *stream);
+/* Replaces sphrt_trace_normal_f64 in the same way: yhat is bitwise the float64 forward, r the
+ * same two roundings, r * len one more, then quantised and added as above.  acc, record,
+ * refusals and cost as sphrt_trace_backproject_fixed_f64 (and sphrt_trace_normal_f64's own
+ * refusals). */
+int sphrt_trace_normal_fixed_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                                 const double *density, const double *m, double scale,
+                                 int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+                                 double *yhat, int64_t y_chan_stride, int64_t *acc,
+                                 const void *scale_rec,
+                                 void *workspace, size_t workspace_size, void *stream);
+/* out[j] = the value of element j (acc[2j], acc[2j + 1]) under *scale_rec, one thread per
+ * element; what reading the float64 accumulator of the entries it replaces was.  Fails on the
+ * host on a null record, a negative n_elems and (n_elems > 0) a null acc or out. */
+int sphrt_fixed_finalize_f64(const int64_t *acc, int64_t n_elems, const void *scale_rec,
+                             double *out, void *stream);
+/* Host-only mirrors of the arithmetic above (the same functions the kernels compile), for tests
+ * and callers that need to predict bits.  sphrt_fixed_exponent_host: E and flags of a bound
+ * (fails on a negative bound or a null output); sphrt_fixed_quantise_host: lo_hi = the split
+ * quanta of one term; sphrt_fixed_value_host: the value of a {lo, hi} pair. */
+int sphrt_fixed_exponent_host(double bound, int32_t *E, int32_t *flags);
+void sphrt_fixed_quantise_host(double term, int32_t E, int64_t lo_hi[2]);
+double sphrt_fixed_value_host(int64_t lo, int64_t hi, int32_t E, int32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

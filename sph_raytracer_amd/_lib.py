@@ -141,6 +141,17 @@ _SIGNATURES = [
     ('sphrt_trace_normal_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_dbl,
                                        c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
                                        ctypes.c_size_t, c_vp]),
+    ('sphrt_fixed_scale_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_i64, c_dbl, c_vp, c_vp]),
+    ('sphrt_trace_backproject_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_i64,
+                                                  c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                                  ctypes.c_size_t, c_vp]),
+    ('sphrt_trace_normal_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_dbl,
+                                             c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                             ctypes.c_size_t, c_vp]),
+    ('sphrt_fixed_finalize_f64', c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    ('sphrt_fixed_exponent_host', c_int, [c_dbl, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    ('sphrt_fixed_quantise_host', None, [c_dbl, c_i32, ctypes.POINTER(c_i64)]),
+    ('sphrt_fixed_value_host', c_dbl, [c_i64, c_i64, c_i32, c_i32]),
 ]
 EXPORTED = [s[0] for s in _SIGNATURES]
 TRACE_F32, TRACE_INVALID, TRACE_FRESH_RAYS = 1, 2, 4   # sphrt_trace_reference flags (sphrt.h)

@@ -18,8 +18,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'lib', 'libsphrt.so')
 FAST_OUT = os.path.join(HERE, 'lib', '_sphrt_fast.so')   # CPython entry for steady-state calls
-SOURCES = ['api.hip', 'trace.hip', 'apply.hip', 'transpose.hip', 'rays.hip', 'loss.hip']
-HEADERS = ['common.hpp', 'solve.hpp', 'introsort.hpp', 'stage.hpp']
+SOURCES = ['api.hip', 'trace.hip', 'apply.hip', 'transpose.hip', 'rays.hip', 'loss.hip',
+           'fixed.hip']
+HEADERS = ['common.hpp', 'solve.hpp', 'introsort.hpp', 'stage.hpp', 'fixed.hpp']
 ARCH = os.environ.get('SPHRT_ARCH', 'gfx950')
 
 

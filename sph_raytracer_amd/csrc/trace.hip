@@ -30,6 +30,7 @@
 #include <climits>
 
 #include "common.hpp"
+#include "fixed.hpp"
 #include "introsort.hpp"
 #include "solve.hpp"
 
@@ -43,8 +44,15 @@ namespace sphrt {
 // out[ray] = sum rho[vox] * len.  NORMAL: both on one trace, the gradient of a squared residual
 // (the normal equations' A^T(s (A x - m))) — INTEGRATE's sum, written to out, then
 // acc[vox] += ((out[ray] - m[ray]) * scale) * len over the same segments.
+// SCATTER_FIXED / NORMAL_FIXED: the same two with every term y * len quantised onto the power-of-
+// two grid of the caller's scale record and added as two 64-bit integer atomics into a
+// {lo, hi} pair per voxel (fixed.hpp): integer sums, so the result is bitwise independent of the
+// order of the adds.  out (NORMAL_FIXED) is the same float64 forward.
 enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4,
-       MODE_SCATTER = 5, MODE_NORMAL = 6 };
+       MODE_SCATTER = 5, MODE_NORMAL = 6, MODE_SCATTER_FIXED = 7, MODE_NORMAL_FIXED = 8 };
+constexpr bool mode_scatter(int m) { return m == MODE_SCATTER || m == MODE_SCATTER_FIXED; }
+constexpr bool mode_normal(int m) { return m == MODE_NORMAL || m == MODE_NORMAL_FIXED; }
+constexpr bool mode_fixed(int m) { return m == MODE_SCATTER_FIXED || m == MODE_NORMAL_FIXED; }
 constexpr int kNone = 0x7fffffff;  // "no update" in the forward-fill scans
 constexpr int kWavesPerBlock = 4;
 
@@ -432,7 +440,40 @@ struct TraceOut {
     int wedge;                       // solve only the half-planes of a line's azimuth wedge
     const double* meas;       // NORMAL: the measurements, laid out as out (out_chan_stride apart)
     double scale;             // NORMAL: the residual's factor
+    const int32_t* fixed_rec; // *_FIXED: the scale record {E, flags, pad}; acc is then the
+                              // int64 {lo, hi} pairs, 2 * chan_stride int64 per channel
 };
+
+// *_FIXED: what a wave reads of the scale record, once per ray it emits (a uniform load: scalar
+// registers), never per segment.  live: terms are added (flags == 0).
+struct FixedAdd {
+    int shift;      // 61 - E
+    bool live;
+};
+template <int MODE, typename T>
+__device__ __forceinline__ FixedAdd fixed_add_of(const TraceOut<T>& o) {
+    FixedAdd f{0, true};
+    if constexpr (mode_fixed(MODE)) {
+        f.shift = kFixedBits - o.fixed_rec[0];
+        f.live = o.fixed_rec[1] == 0;
+    }
+    return f;
+}
+
+// acc[idx] += term: one float64 atomic, or (*_FIXED) the term in quanta, split, as two 64-bit
+// integer atomics without return on the element's {lo, hi} pair.
+template <int MODE>
+__device__ __forceinline__ void acc_add(double* acc, int64_t idx, double term, const FixedAdd& f) {
+    if constexpr (mode_fixed(MODE)) {
+        int64_t lo, hi;
+        fixed_quantise(term, f.shift, lo, hi);
+        unsigned long long* p = reinterpret_cast<unsigned long long*>(acc) + 2 * idx;
+        atomicAdd(p, (unsigned long long)lo);
+        atomicAdd(p + 1, (unsigned long long)hi);
+    } else {
+        atomicAdd(acc + idx, term);
+    }
+}
 
 // EMIT: ray `ray` has `cnt` segments; its staging slot is [row_ptr[ray], row_ptr[ray + 1]) (the
 // scanned bounds).  Returns the slot start, or -1 (counted in n_over) when they do not fit.
@@ -455,11 +496,13 @@ __device__ __forceinline__ int64_t emit_slot(const TraceOut<T>& o, int64_t ray, 
 // SCATTER: a ray's compacted segments (seg_vox, seg_len: nseg of them, in LDS) and its head
 // segment (hlen in voxel hvox, when `head`) added into the accumulator by the whole wave — every
 // channel's y[c][ray] (static, multichannel), or y[ray] into time slice ray / ray_chan_div.
-template <typename T>
+template <int MODE, typename T>
 __device__ __forceinline__ void scatter_segments(const TraceOut<T>& o, int64_t ray, int lane,
                                                  int nseg, const int32_t* seg_vox,
                                                  const double* seg_len, bool head, int hvox,
                                                  double hlen) {
+    const FixedAdd fx = fixed_add_of<MODE>(o);
+    if (!fx.live) return;
     int64_t c_lo = 0, c_hi = o.n_chan;
     if (o.ray_chan_div > 0) {
         c_lo = ray / o.ray_chan_div;
@@ -468,9 +511,9 @@ __device__ __forceinline__ void scatter_segments(const TraceOut<T>& o, int64_t r
     for (int64_t c = c_lo; c < c_hi; ++c) {
         const int64_t yc = o.ray_chan_div > 0 ? 0 : c;
         const double yv = (double)o.density[yc * o.out_chan_stride + ray];
-        double* acc = o.acc + c * o.chan_stride;
-        if (head && lane == 0) atomicAdd(acc + hvox, yv * hlen);
-        for (int q = lane; q < nseg; q += 64) atomicAdd(acc + seg_vox[q], yv * seg_len[q]);
+        double* acc = o.acc + (mode_fixed(MODE) ? 2 : 1) * c * o.chan_stride;
+        if (head && lane == 0) acc_add<MODE>(acc, hvox, yv * hlen, fx);
+        for (int q = lane; q < nseg; q += 64) acc_add<MODE>(acc, seg_vox[q], yv * seg_len[q], fx);
     }
 }
 
@@ -479,11 +522,12 @@ __device__ __forceinline__ void scatter_segments(const TraceOut<T>& o, int64_t r
 // wave_sum, the same products in the same order — and goes to out; every lane then holds it and
 // forms the residual r = (sum - m) * scale (two roundings, sphrt_sq_residual_f64's), which is
 // scattered as SCATTER scatters y.
-template <typename T>
+template <int MODE, typename T>
 __device__ __forceinline__ void normal_segments(const TraceOut<T>& o, int64_t ray, int lane,
                                                 int nseg, const int32_t* seg_vox,
                                                 const double* seg_len, bool head, int hvox,
                                                 double hlen) {
+    const FixedAdd fx = fixed_add_of<MODE>(o);
     int64_t c_lo = 0, c_hi = o.n_chan;
     if (o.ray_chan_div > 0) {
         c_lo = ray / o.ray_chan_div;
@@ -498,9 +542,10 @@ __device__ __forceinline__ void normal_segments(const TraceOut<T>& o, int64_t ra
         const int64_t oc = (o.ray_chan_div > 0) ? 0 : c;
         if (lane == 0) o.out[oc * o.out_chan_stride + ray] = (T)sum;
         const double r = (sum - o.meas[oc * o.out_chan_stride + ray]) * o.scale;
-        double* acc = o.acc + c * o.chan_stride;
-        if (head && lane == 0) atomicAdd(acc + hvox, r * hlen);
-        for (int q = lane; q < nseg; q += 64) atomicAdd(acc + seg_vox[q], r * seg_len[q]);
+        if (!fx.live) continue;
+        double* acc = o.acc + (mode_fixed(MODE) ? 2 : 1) * c * o.chan_stride;
+        if (head && lane == 0) acc_add<MODE>(acc, hvox, r * hlen, fx);
+        for (int q = lane; q < nseg; q += 64) acc_add<MODE>(acc, seg_vox[q], r * seg_len[q], fx);
     }
 }
 
@@ -1072,11 +1117,11 @@ __device__ void trace_one(const GridDev& G, const RayGeo& g, const double t1c_o,
             o.vox[r0 + head + q] = seg_vox[q];
             o.len[r0 + head + q] = seg_len[q];
         }
-    } else if (MODE == MODE_SCATTER) {
-        scatter_segments(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
+    } else if (mode_scatter(MODE)) {
+        scatter_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
                          (sr * G.ne + se) * G.na + sa, -tneg);
-    } else if (MODE == MODE_NORMAL) {
-        normal_segments(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
+    } else if (mode_normal(MODE)) {
+        normal_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
                         (sr * G.ne + se) * G.na + sa, -tneg);
     } else {
         const int svox = (sr * G.ne + se) * G.na + sa;
@@ -1255,7 +1300,7 @@ __global__ __launch_bounds__(256) void screen_kernel(GridDev G, RaysDev R, Trace
                             : 0;
     if (active && !hit) {
         if (MODE == MODE_COUNT) o.counts[ray] = 0;
-        if (MODE == MODE_INTEGRATE || MODE == MODE_NORMAL) {
+        if (MODE == MODE_INTEGRATE || mode_normal(MODE)) {
             const int64_t nc = o.ray_chan_div > 0 ? 1 : o.n_chan;
             for (int64_t c = 0; c < nc; ++c) o.out[c * o.out_chan_stride + ray] = (T)0;
         }
@@ -1448,16 +1493,17 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
     const int K = G.K, r_lim = 2 * G.nbr, e_lim = 2 * G.nbr + 2 * G.nbe;
     // NORMAL: INTEGRATE's walks (one per channel, each writing out), then one more (scat) that
     // scatters the residuals of what this lane just wrote
-    constexpr bool kSum = MODE == MODE_INTEGRATE || MODE == MODE_NORMAL;
+    constexpr bool kSum = MODE == MODE_INTEGRATE || mode_normal(MODE);
+    const FixedAdd fx = fixed_add_of<MODE>(o);   // (read once per ray, not per segment)
     int64_t c_lo = 0, c_hi = o.n_chan;
     if (kSum && o.ray_chan_div > 0) {
         c_lo = ray / o.ray_chan_div;
         c_hi = c_lo + 1;
     }
     if (!kSum) c_hi = c_lo + 1;
-    const int64_t c_end = MODE == MODE_NORMAL ? c_hi + 1 : c_hi;
+    const int64_t c_end = mode_normal(MODE) ? c_hi + 1 : c_hi;
     for (int64_t c = c_lo; c < c_end; ++c) {
-        const bool scat = MODE == MODE_NORMAL && c == c_hi;
+        const bool scat = mode_normal(MODE) && c == c_hi;
         int cr = s[0], ce = s[1], ca = s[2];
         int64_t nseg = 0;
         double acc = 0.0;
@@ -1485,20 +1531,21 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
                 o.len[base + nseg] = len;
             } else if (kSum && !scat) {
                 acc += (double)o.density[c * o.chan_stride + vx] * len;
-            } else if (MODE == MODE_NORMAL) {
-                for (int64_t ch = c_lo; ch < c_hi; ++ch) {
+            } else if (mode_normal(MODE)) {
+                for (int64_t ch = c_lo; fx.live && ch < c_hi; ++ch) {
                     const int64_t oc = (o.ray_chan_div > 0 ? 0 : ch) * o.out_chan_stride + ray;
                     const double r = ((double)o.out[oc] - o.meas[oc]) * o.scale;
-                    atomicAdd(o.acc + ch * o.chan_stride + vx, r * len);
+                    acc_add<MODE>(o.acc, ch * o.chan_stride + vx, r * len, fx);
                 }
-            } else if (MODE == MODE_SCATTER) {   // (one walk: every channel per segment)
-                if (o.ray_chan_div > 0) {
-                    atomicAdd(o.acc + (ray / o.ray_chan_div) * o.chan_stride + vx,
-                              (double)o.density[ray] * len);
+            } else if (mode_scatter(MODE)) {   // (one walk: every channel per segment)
+                if (!fx.live) {
+                } else if (o.ray_chan_div > 0) {
+                    acc_add<MODE>(o.acc, (ray / o.ray_chan_div) * o.chan_stride + vx,
+                                  (double)o.density[ray] * len, fx);
                 } else {
                     for (int64_t ch = 0; ch < o.n_chan; ++ch)
-                        atomicAdd(o.acc + ch * o.chan_stride + vx,
-                                  (double)o.density[ch * o.out_chan_stride + ray] * len);
+                        acc_add<MODE>(o.acc, ch * o.chan_stride + vx,
+                                      (double)o.density[ch * o.out_chan_stride + ray] * len, fx);
                 }
             }
             ++nseg;
@@ -1570,10 +1617,10 @@ __device__ void exact_walk_wave(const GridDev& G, const TraceOut<T>& o, int64_t 
             o.vox[r0 + q] = seg_vox[q];
             o.len[r0 + q] = seg_len[q];
         }
-    } else if (MODE == MODE_SCATTER) {
-        scatter_segments(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
-    } else if (MODE == MODE_NORMAL) {
-        normal_segments(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
+    } else if (mode_scatter(MODE)) {
+        scatter_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
+    } else if (mode_normal(MODE)) {
+        normal_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
     } else {
         int64_t c_lo = 0, c_hi = o.n_chan;
         if (o.ray_chan_div > 0) {
@@ -2391,6 +2438,92 @@ extern "C" int sphrt_trace_normal_f64(const sphrt_plan* plan, const sphrt_rays* 
     o.scale = scale;
     return launch_trace<MODE_NORMAL, double>(G, R, o, workspace, workspace_size,
                                              (hipStream_t)stream);
+}
+
+// What the fixed-point entries refuse on top of refuse_fused, on the host: a null scale record,
+// and a batch that could exhaust a voxel's capacity of 2^31 adds (fixed.hpp) — every ray adds to
+// a voxel at most a few times per channel, so n_rays * n_chan < 2^29 keeps any number of such
+// calls a caller is likely to make into one accumulator below it.
+constexpr int64_t kFixedBatchCap = (int64_t)1 << 29;
+static int refuse_fixed(const sphrt_plan* plan, const sphrt_rays* rays, int64_t n_chan,
+                        const void* scale_rec) {
+    if (!plan) return fail("null plan");
+    if (!rays) return fail("null ray batch");
+    if (!scale_rec) return fail("null scale record");
+    if (rays->ndim < 0 || rays->ndim > kMaxDims) return 0;     // (refuse_fused's message)
+    int64_t n = 1;
+    for (int d = 0; d < rays->ndim; ++d) {
+        if (rays->shape[d] < 0) return 0;
+        // (n stays below the cap: no overflow whatever the extents are)
+        if (rays->shape[d] >= kFixedBatchCap || (n *= rays->shape[d]) >= kFixedBatchCap)
+            return fail("%lld or more rays exceed the fixed-point capacity of 2^29 adds per call",
+                        (long long)n);
+    }
+    if (n * (n_chan > 1 ? n_chan : 1) >= kFixedBatchCap || n_chan >= kFixedBatchCap)
+        return fail("%lld rays x %lld channels exceed the fixed-point capacity of 2^29 adds per "
+                    "call", (long long)n, (long long)n_chan);
+    return 0;
+}
+
+extern "C" int sphrt_trace_backproject_fixed_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                                 const double* y, int64_t n_chan,
+                                                 int64_t y_chan_stride, int64_t ray_chan_div,
+                                                 int64_t* acc, int64_t chan_stride,
+                                                 const void* scale_rec, void* workspace,
+                                                 size_t workspace_size, void* stream) {
+    if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
+    if (int e = refuse_fused(plan, rays,
+                             !y || !acc ? "null back-projection argument (y or acc)" : nullptr,
+                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
+                             workspace_size))
+        return e;
+    GridDev G;
+    RaysDev R;
+    if (int e = resolve(plan, rays, G, R, stream)) return e;
+    DeviceGuard guard(plan->device);
+    TraceOut<double> o{};
+    o.density = y;
+    o.n_chan = n_chan;
+    o.chan_stride = chan_stride;
+    o.ray_chan_div = ray_chan_div;
+    o.out_chan_stride = y_chan_stride;
+    o.acc = reinterpret_cast<double*>(acc);
+    o.fixed_rec = static_cast<const int32_t*>(scale_rec);
+    return launch_trace<MODE_SCATTER_FIXED, double>(G, R, o, workspace, workspace_size,
+                                                    (hipStream_t)stream);
+}
+
+extern "C" int sphrt_trace_normal_fixed_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                            const double* density, const double* m, double scale,
+                                            int64_t n_chan, int64_t chan_stride,
+                                            int64_t ray_chan_div, double* yhat,
+                                            int64_t y_chan_stride, int64_t* acc,
+                                            const void* scale_rec, void* workspace,
+                                            size_t workspace_size, void* stream) {
+    if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
+    if (int e = refuse_fused(plan, rays,
+                             !density || !m || !yhat || !acc
+                                 ? "null normal argument (density, m, yhat or acc)" : nullptr,
+                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
+                             workspace_size))
+        return e;
+    GridDev G;
+    RaysDev R;
+    if (int e = resolve(plan, rays, G, R, stream)) return e;
+    DeviceGuard guard(plan->device);
+    TraceOut<double> o{};
+    o.density = density;
+    o.n_chan = n_chan;
+    o.chan_stride = chan_stride;
+    o.ray_chan_div = ray_chan_div;
+    o.out = yhat;
+    o.out_chan_stride = y_chan_stride;
+    o.acc = reinterpret_cast<double*>(acc);
+    o.meas = m;
+    o.scale = scale;
+    o.fixed_rec = static_cast<const int32_t*>(scale_rec);
+    return launch_trace<MODE_NORMAL_FIXED, double>(G, R, o, workspace, workspace_size,
+                                                   (hipStream_t)stream);
 }
 
 template <typename F>

@@ -980,11 +980,36 @@ def _fused_forward(parts, grid, density, dev):
     return out.reshape(out_shape).to(device=density.device, dtype=density.dtype)
 
 
-def _fused_adjoint(parts, grid, y, dshape, rdtype, rdevice, dev):
+def _fixed_buffers(n_elems, dev):
+    """The fixed-point accumulator of a deterministic call — an int64 {lo, hi} pair per density
+    element, zeroed — and its 16-byte scale record (csrc/fixed.hpp)."""
+    return (tr.zeros(2 * n_elems, dtype=tr.int64, device=dev),
+            tr.zeros(2, dtype=tr.int64, device=dev))
+
+
+def _outer_diameter(grid):
+    """L = 2 r_b[nr], what the fixed-point scale is taken from: no segment between two crossings
+    of a unit direction is longer (a head segment or a shorter direction's segments may be, and
+    are still added exactly: csrc/fixed.hpp, fixed_quantise)."""
+    return 2.0 * float(grid.r_b[-1])
+
+
+def _fixed_finalize(fixed, out, dev):
+    """The accumulator's values under its record -> float64 `out` (sphrt_fixed_finalize_f64)."""
+    iacc, rec = fixed
+    _lib.check(_lib.load().sphrt_fixed_finalize_f64(
+        _lib.ptr(iacc), out.numel(), _lib.ptr(rec), _lib.ptr(out), _lib.stream_of(dev)),
+        'sphrt_fixed_finalize_f64')
+    return out
+
+
+def _fused_adjoint(parts, grid, y, dshape, rdtype, rdevice, dev, deterministic=False):
     """Back-projection of y into a `dshape` volume over prebuilt parts
-    (sphrt_trace_backproject_f64: the trace again, float64 atomics into a zeroed accumulator).
-    y goes in as float64 (from float32 for dtypes that are neither); the result is rounded to
-    `rdtype` (float32: sphrt_f64_to_f32) and left on `rdevice`."""
+    (sphrt_trace_backproject_f64: the trace again, float64 atomics into a zeroed accumulator; or
+    with `deterministic` the scale of max|y| L, sphrt_trace_backproject_fixed_f64 into a zeroed
+    integer accumulator and its finalize pass).  y goes in as float64 (from float32 for dtypes
+    that are neither); the result is rounded to `rdtype` (float32: sphrt_f64_to_f32) and left on
+    `rdevice`."""
     plan, batch, ws = parts
     n_chan, div, _ = _layout_for(grid, batch.shape, dshape)
     n = batch.n
@@ -993,6 +1018,19 @@ def _fused_adjoint(parts, grid, y, dshape, rdtype, rdevice, dev):
     if yv.numel() != n_chan * n:
         raise ValueError(f'adjoint input has {yv.numel()} values, expected {n_chan * n}')
     lib = _lib.load()
+    if deterministic:
+        stream = _lib.stream_of(dev)
+        fixed = _fixed_buffers(math.prod(dshape), dev)
+        _lib.check(lib.sphrt_fixed_scale_f64(_lib.ptr(yv), yv.numel(), _outer_diameter(grid),
+                                             None, 0, 0.0, _lib.ptr(fixed[1]), stream),
+                   'sphrt_fixed_scale_f64')
+        _lib.check(lib.sphrt_trace_backproject_fixed_f64(
+            plan.handle, batch.desc, _lib.ptr(yv), n_chan, n, div, _lib.ptr(fixed[0]),
+            math.prod(grid.shape[-3:]), _lib.ptr(fixed[1]), _lib.ptr(ws), ws.numel(), stream),
+            'sphrt_trace_backproject_fixed_f64')
+        acc = _fixed_finalize(fixed, tr.empty(math.prod(dshape), dtype=tr.float64, device=dev),
+                              dev)
+        return _from_f64(acc, rdtype, dev).reshape(dshape).to(rdevice)
     acc = tr.zeros(math.prod(dshape), dtype=tr.float64, device=dev)
     _lib.check(lib.sphrt_trace_backproject_f64(
         plan.handle, batch.desc, _lib.ptr(yv), n_chan, n, div, _lib.ptr(acc),
@@ -1031,24 +1069,44 @@ def _gradient_layout(grid, ray_shape, dshape, mshape):
     return n_chan, div, tuple(int(v) for v in mshape)
 
 
-def _launch_normal(parts, grid, d, m, scale, n_chan, div, yhat, acc, dev):
+def _launch_normal(parts, grid, d, m, scale, n_chan, div, yhat, acc, dev, fixed=None):
     """sphrt_trace_normal_f64 over prebuilt parts: flat float64 d and m on `dev`; yhat receives
-    A d, the zeroed acc gains A^T(scale (A d - m))."""
+    A d, the zeroed acc gains A^T(scale (A d - m)).  With `fixed` (_fixed_buffers, the
+    accumulator zeroed) the deterministic form: the scale of |scale| (max|d| L + max|m|) L,
+    sphrt_trace_normal_fixed_f64 into the integer accumulator, and its values written to acc
+    (which need not be zeroed); nothing is allocated."""
     plan, batch, ws = parts
+    if fixed is not None:
+        lib, stream = _lib.load(), _lib.stream_of(dev)
+        L, s = _outer_diameter(grid), abs(float(scale))
+        _lib.check(lib.sphrt_fixed_scale_f64(_lib.ptr(d), d.numel(), s * L * L, _lib.ptr(m),
+                                             m.numel(), s * L, _lib.ptr(fixed[1]), stream),
+                   'sphrt_fixed_scale_f64')
+        _lib.check(lib.sphrt_trace_normal_fixed_f64(
+            plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), scale, n_chan,
+            math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(fixed[0]),
+            _lib.ptr(fixed[1]), _lib.ptr(ws), ws.numel(), stream), 'sphrt_trace_normal_fixed_f64')
+        _fixed_finalize(fixed, acc, dev)
+        return
     _lib.check(_lib.load().sphrt_trace_normal_f64(
         plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), scale, n_chan,
         math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(acc), _lib.ptr(ws),
         ws.numel(), _lib.stream_of(dev)), 'sphrt_trace_normal_f64')
 
 
-def _fused_gradient(parts, grid, density, m, scale, dev):
+def _fused_gradient(parts, grid, density, m, scale, dev, deterministic=False):
     """(A density, A^T(scale (A density - m))) from one trace over prebuilt parts, computed in
     float64 and returned in density's dtype on density's device."""
     n_chan, div, out_shape = _gradient_layout(grid, parts[1].shape, density.shape, m.shape)
     d, mv = _to_f64(density, dev), _to_f64(m, dev)
     yhat = tr.empty(mv.numel(), dtype=tr.float64, device=dev)
-    acc = tr.zeros(d.numel(), dtype=tr.float64, device=dev)
-    _launch_normal(parts, grid, d, mv, float(scale), n_chan, div, yhat, acc, dev)
+    if deterministic:
+        acc = tr.empty(d.numel(), dtype=tr.float64, device=dev)
+        _launch_normal(parts, grid, d, mv, float(scale), n_chan, div, yhat, acc, dev,
+                       _fixed_buffers(d.numel(), dev))
+    else:
+        acc = tr.zeros(d.numel(), dtype=tr.float64, device=dev)
+        _launch_normal(parts, grid, d, mv, float(scale), n_chan, div, yhat, acc, dev)
     rdt, rdev = density.dtype, density.device
     return (_from_f64(yhat, rdt, dev).reshape(out_shape).to(rdev),
             _from_f64(acc, rdt, dev).reshape(density.shape).to(rdev))
@@ -1060,15 +1118,24 @@ def _time_slices_rule(grid, time_slices):
         raise NotImplementedError
 
 
-def back_project(grid, geom, y, *, time_slices=None):
+def back_project(grid, geom, y, *, time_slices=None, deterministic=False):
     """No-store adjoint, the sibling of ``line_integrals``: trace and scatter in one fused pass,
     nothing persisted.
 
-    Same result as ``Operator(grid, geom).T(y)`` with ``adjoint_mode='atomic'`` (float64 atomics:
-    within rounding of it, not bitwise reproducible) without building the segment CSR.  Static
-    grid: y (C..., *geom.shape) -> (C..., nr, ne, na).  Dynamic grid: y (T, ...) -> (T, nr, ne,
-    na) under the rules of ``Operator.T(y, time_slices=True)`` (time_slices=None takes them for a
-    dynamic grid; False raises as ``Operator.T`` does).  The result has y's dtype and device."""
+    Same result as ``Operator(grid, geom).T(y)`` with ``adjoint_mode='atomic'``, within rounding,
+    without building the segment CSR.  Two modes.  ``deterministic=False`` (default) sums
+    ``y * len`` with float64 atomics: one atomic per segment, 8 bytes per density element, and
+    last bits that change from run to run.  ``deterministic=True`` quantises every ``y * len``
+    onto one power-of-two grid, 2^-61 of a bound on the largest term (max|y| times the outer
+    sphere's diameter), and sums integers: bitwise the same result whatever the ray order, the
+    schedule or the run, with an absolute error no larger than the float64 sum's — at the cost
+    of 16 more bytes per density element during the call and two integer atomics per segment
+    instead of one float64 atomic.  One inf or NaN in y then makes the whole result NaN (the
+    atomic mode poisons only the voxels it reaches); a batch of 2^29 or more rays x channels is
+    refused.  Static grid: y (C..., *geom.shape) -> (C..., nr, ne, na).  Dynamic grid: y (T, ...)
+    -> (T, nr, ne, na) under the rules of ``Operator.T(y, time_slices=True)`` (time_slices=None
+    takes them for a dynamic grid; False raises as ``Operator.T`` does).  The result has y's
+    dtype and device."""
     y = tr.as_tensor(y)
     _time_slices_rule(grid, grid.dynamic if time_slices is None else time_slices)
     _, _, dshape = _adjoint_layout(grid, geom.shape, y.shape)    # (before any device is touched)
@@ -1076,7 +1143,8 @@ def back_project(grid, geom, y, *, time_slices=None):
     with tr.cuda.device(dev):
         parts = _fused_parts(grid, geom, dev)
         _adjoint_layout(grid, parts[1].shape, y.shape)
-        return _fused_adjoint(parts, grid, y, dshape, y.dtype, y.device, dev)
+        return _fused_adjoint(parts, grid, y, dshape, y.dtype, y.device, dev,
+                              bool(deterministic))
 
 
 # switches of the Python construction sequence: any of them set keeps Operator construction in
@@ -2056,17 +2124,27 @@ class MatrixFreeOperator:
         compute runs on the GPU it names, else the current one).  ftype=float32 and invalid=True
         (the reference-mode traces) are not available here: use ``Operator``.
     ``op(density)`` equals ``line_integrals`` and is differentiable; ``op.T(y)`` follows
-    ``Operator.T`` (and also takes leading channel axes on a static grid).  The adjoint sums
-    with float64 atomics: within rounding of ``Operator.T``, not bitwise reproducible.
+    ``Operator.T`` (and also takes leading channel axes on a static grid).  The adjoint is within
+    rounding of ``Operator.T`` in either of two modes, chosen by ``deterministic`` (an argument
+    and an attribute that may be set at any time): False (default) sums with float64 atomics —
+    one atomic per segment, last bits that differ from run to run; True sums every term as an
+    integer on one power-of-two grid (``back_project``'s deterministic mode, csrc/fixed.hpp) —
+    bitwise reproducible whatever the ray order or schedule, for 16 more bytes per density
+    element per call and two integer atomics per segment instead of one float64 atomic.  The
+    attribute governs ``T``, the backward of ``op(x)``, ``residual_gradient`` and gd()'s loop.
     ``op.residual_gradient(density, m, scale)`` gives ``op(density)`` and
     ``op.T(scale * (op(density) - m))`` from one trace instead of two.  There are
     no ``regs`` / ``lens`` / ``segments`` views: nothing is stored to show.  The workspace is
     shared by the calls: use an operator from one stream at a time."""
 
-    def __init__(self, grid, geom, dynamic=False, ftype=FTYPE, device=DEVICE, invalid=False):
+    deterministic = False
+
+    def __init__(self, grid, geom, dynamic=False, ftype=FTYPE, device=DEVICE, invalid=False,
+                 deterministic=False):
         if ftype != tr.float64 or invalid:
             raise NotImplementedError('MatrixFreeOperator traces in float64 with masking only; '
                                       'ftype=float32 and invalid=True need Operator')
+        self.deterministic = bool(deterministic)
         self.grid = grid
         self.geom = geom
         if dynamic is None:
@@ -2099,7 +2177,7 @@ class MatrixFreeOperator:
     def _apply_adjoint(self, y, dshape, ddtype, ddevice):
         with tr.cuda.device(self._cdev):
             return _fused_adjoint(self._parts, self.grid, y, tuple(dshape), ddtype, ddevice,
-                                  self._cdev)
+                                  self._cdev, bool(self.deterministic))
 
     def T(self, line_integrations, *, time_slices=False):
         """Back-projection of ``line_integrations`` into a grid.shape volume, as ``Operator.T``:
@@ -2120,18 +2198,35 @@ class MatrixFreeOperator:
         ``measurements`` has ``op(density)``'s shape.  Static grids take leading channel axes; a
         dynamic grid pairs time slices with views as the forward does, so ``grad`` is autograd's
         gradient of the dynamic forward.  Computed in float64 (``yhat`` is bitwise the float64
-        forward; ``grad`` sums with float64 atomics) and returned in ``density``'s dtype on its
+        forward; ``grad`` sums with float64 atomics, or with ``op.deterministic`` set as integers
+        on one power-of-two grid — sphrt_trace_normal_fixed_f64, bitwise reproducible, 16 more
+        bytes per density element during the call) and returned in ``density``'s dtype on its
         device.  Not differentiable."""
         density, m = tr.as_tensor(density), tr.as_tensor(measurements)
         _gradient_layout(self.grid, self._ray_shape, density.shape, m.shape)   # (host only)
         with tr.cuda.device(self._cdev):
-            return _fused_gradient(self._parts, self.grid, density, m, scale, self._cdev)
+            return _fused_gradient(self._parts, self.grid, density, m, scale, self._cdev,
+                                   bool(self.deterministic))
 
-    def _normal_into(self, d, m, scale, yhat, acc):
+    def _fixed_buffers(self):
+        """What a deterministic _normal_into adds into: the integer accumulator of a grid.shape
+        density and its scale record, for the caller to allocate once and hand to every call."""
+        with tr.cuda.device(self._cdev):
+            return _fixed_buffers(math.prod(self.grid.shape), self._cdev)
+
+    def _normal_into(self, d, m, scale, yhat, acc, fixed=None):
         """residual_gradient for gd's fused loop (retrieval._gd_direct): a grid.shape float64
         density and flat float64 measurements on the compute device, into the caller's yhat and
-        zeroed acc; nothing allocated."""
-        _launch_normal(self._parts, self.grid, d, m, scale, 1, 0, yhat, acc, self._cdev)
+        zeroed acc; nothing allocated.  With ``deterministic`` set, through `fixed` (the caller's
+        _fixed_buffers(), zeroed here; without them a pair is allocated for the call)."""
+        if self.deterministic:
+            if fixed is None:
+                fixed = self._fixed_buffers()
+            else:
+                fixed[0].zero_()
+        else:
+            fixed = None
+        _launch_normal(self._parts, self.grid, d, m, scale, 1, 0, yhat, acc, self._cdev, fixed)
 
     def __repr__(self):
         if self.dynamic:

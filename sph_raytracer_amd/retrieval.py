@@ -136,7 +136,9 @@ def _direct_plan(f, y, model, coeffs, loss_fns, optim_vars):
 def _fused_plan(f, y, model, coeffs, loss_fns, optim_vars):
     """`_direct_plan` for a MatrixFreeOperator on a static grid: the same loop and the same
     conditions, with the forward and the adjoint of an iteration in one trace
-    (MatrixFreeOperator.residual_gradient's kernel).  Anything else takes the autograd loop."""
+    (MatrixFreeOperator.residual_gradient's kernel; the operator's `deterministic` attribute
+    picks the float64-atomic or the fixed-point scatter, and with the latter two runs of gd give
+    the same bits).  Anything else takes the autograd loop."""
     from .raytracer import MatrixFreeOperator
     if not isinstance(f, MatrixFreeOperator) or f.dynamic or f.grid.dynamic or y is None:
         return None
@@ -239,6 +241,9 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
         if loop_desc is not None or fused else None
     # the fused trace subtracts float64 measurements (a float32 y promoted once, exactly)
     m64 = yd.to(t.float64).reshape(-1) if fused else None
+    # a deterministic operator's integer accumulator and scale record, once for the whole loop
+    # (every iteration: scale, the fixed-point trace, finalize into g — nothing allocated)
+    fixed = (f._fixed_buffers(),) if fused and f.deterministic else ()
     # every iteration's loss as the workgroup partial sums of its fused kernel, one row per
     # iteration, summed once after the loop (no reduction launch, no host sync per iteration)
     ps, pn = lib.sphrt_loss_partials(n_meas), lib.sphrt_loss_partials(n_vox)
@@ -264,7 +269,7 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                     # f(d) into yhat_buf and A^T((f(d) - y) * (2 lam / N)) into a zeroed g from
                     # one trace; the residual launch below then only sums the loss
                     g = t.zeros_like(d)
-                    f._normal_into(d, m64, 2 * c_sq, yhat_buf, g)
+                    f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed)
                     yhat = yhat_buf.view(yd.shape)
                 elif loop_desc is not None:
                     # (staged: the forward reads the brick copy the previous Adam launch wrote;

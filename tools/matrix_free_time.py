@@ -5,6 +5,8 @@ trace + scatter) beside the stored-trace Operator, on one GPU.
     python tools/matrix_free_time.py [--configs c2 c3] [--out profiles/matrix_free_times.json]
     python tools/matrix_free_time.py --gradient [--configs c2 c3] [--gd-config c5]
                                      [--out profiles/matrix_free_gradient_times.json]
+    python tools/matrix_free_time.py --deterministic [--configs c2 c3]
+                                     [--out profiles/matrix_free_deterministic_times.json]
 
 Per config (bench.py's CONFIGS) two legs, each in a fresh child process with its own time limit
 (a leg that fails or runs out of time ends the run: nothing more is started):
@@ -28,6 +30,13 @@ leg; the same child processes and limits):
   gd           ms per iteration of gd(..., 100) over a MatrixFreeOperator on bench.py's C5
                retrieval problem, through the fused loop (retrieval._fused_plan) and through the
                autograd loop (the plan function made to return None), REPEATS times each.
+
+--deterministic measures the fixed-point adjoint beside the float64-atomic one (one leg per
+config, the same child processes and limits):
+  deterministic  float64, in one process: ms per op.T(r) and per op.residual_gradient(x, m) with
+               op.deterministic False and True (HIP events around `reps` calls, REPEATS
+               interleaved rounds, all kept), and the peak of one fused call in each mode.
+               Derived: medians, the ratio of the modes and the spread of the repeats.
 """
 import argparse
 import json
@@ -162,6 +171,68 @@ def leg_gradient(config, reps):
     return rec
 
 
+def leg_deterministic(config, reps):
+    import torch
+    from sph_raytracer_amd import MatrixFreeOperator
+    grid, geom, dev, xs, ys = _problem(config)
+    ts = dict(time_slices=True) if grid.dynamic else {}
+    x, m = xs[torch.float64], ys[torch.float64]
+    op = MatrixFreeOperator(grid, geom, dynamic=grid.dynamic, device=dev)
+    r = 0.5 * (op(x) - m)
+    rec = {'config': config, 'rays': int(op._parts[1].n), 'reps': reps, 'repeats': REPEATS,
+           'dtype': 'float64', 'density_elements': x.numel()}
+    legs = []
+    for det, tag in ((False, 'atomic'), (True, 'deterministic')):
+        def back(det=det):
+            op.deterministic = det
+            return op.T(r, **ts)
+
+        def fused(det=det):
+            op.deterministic = det
+            return op.residual_gradient(x, m, 0.5)
+
+        back(), fused()                                          # warm-up
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        a = fused()
+        torch.cuda.synchronize()
+        rec[f'fused_peak_over_resident_bytes_{tag}'] = torch.cuda.max_memory_allocated(dev) - base
+        del a
+        legs += [(f'backproject_ms_{tag}', back), (f'fused_ms_{tag}', fused)]
+    for name, _ in legs:
+        rec[name] = []
+    for _ in range(REPEATS):                                   # interleaved: one of each per round
+        for name, fn in legs:
+            rec[name].append(events_ms(fn, reps))
+    return rec
+
+
+def derive_deterministic(g):
+    d = {}
+    for what in ('backproject', 'fused'):
+        a, f = g[f'{what}_ms_atomic'], g[f'{what}_ms_deterministic']
+        d[f'{what}_ms_atomic'], d[f'{what}_ms_deterministic'] = _median(a), _median(f)
+        d[f'{what}_deterministic_over_atomic'] = _median(f) / _median(a)
+        d[f'{what}_spread_ms'] = max(max(a) - min(a), max(f) - min(f))
+    return d
+
+
+def main_deterministic(args):
+    out = {}
+    for config in args.configs:
+        rec = _child('deterministic', config, args.reps)
+        if rec is None:
+            return 1
+        out[config] = {'deterministic': rec, 'derived': derive_deterministic(rec)}
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            json.dump(out, fh, indent=1)
+            fh.write('\n')
+    print(json.dumps({c: out[c]['derived'] for c in out}))
+    return 0
+
+
 def leg_gd(config, iterations=100):
     import torch
     import bench
@@ -292,12 +363,15 @@ def main():
                          'profiles/matrix_free_gradient_times.json')
     ap.add_argument('--gradient', action='store_true',
                     help='measure the fused residual back-projection and gd over it instead')
+    ap.add_argument('--deterministic', action='store_true',
+                    help='measure the fixed-point adjoint beside the float64-atomic one instead')
     ap.add_argument('--gd-config', default='c5', help='the gd leg\'s problem (--gradient)')
-    ap.add_argument('--leg', choices=('matrix_free', 'operator', 'gradient', 'gd'),
+    ap.add_argument('--leg', choices=('matrix_free', 'operator', 'gradient', 'gd', 'deterministic'),
                     help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'matrix_free_gradient_times.json'
+        args.out = os.path.join(ROOT, 'profiles', 'matrix_free_deterministic_times.json'
+                                if args.deterministic else 'matrix_free_gradient_times.json'
                                 if args.gradient else 'matrix_free_times.json')
     if args.leg == 'gd':
         print(json.dumps(leg_gd(args.configs[0])))
@@ -305,9 +379,11 @@ def main():
     if args.leg:
         reps = args.reps or (5 if args.configs[0] == 'c3' else 20)
         fn = {'matrix_free': leg_matrix_free, 'operator': leg_operator,
-              'gradient': leg_gradient}[args.leg]
+              'gradient': leg_gradient, 'deterministic': leg_deterministic}[args.leg]
         print(json.dumps(fn(args.configs[0], reps)))
         return 0
+    if args.deterministic:
+        return main_deterministic(args)
     if args.gradient:
         return main_gradient(args)
     out = {}
