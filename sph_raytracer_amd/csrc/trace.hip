@@ -14,10 +14,11 @@
 //   3. the sorted list is scanned (forward fill of the r/e/a rows: in registers, lane-major,
 //      for lists of <= 512 entries), differenced and the non-zero in-grid segments compacted, in
 //      order, back into LDS;
-//   4. depending on MODE the segments are counted, copied to the CSR, integrated against the
-//      density right away (no-store forward), scattered into a float64 accumulator weighted
-//      by the ray's value (no-store adjoint), or both from the one list (the least-squares
-//      gradient: integrate, subtract the measurement, scatter the residual).
+//   4. the list goes to the one segment sink, consume_list: depending on MODE the segments are
+//      counted, copied to the CSR, integrated against the density right away (no-store forward),
+//      scattered into a float64 accumulator weighted by the ray's value (no-store adjoint), or
+//      both from the one list (the least-squares gradient: integrate, subtract the measurement,
+//      scatter the residual).
 // Nothing of size K ever reaches HBM.
 //
 // Exact ties.  The reference orders equal distances the way libstdc++'s introsort happens to
@@ -48,6 +49,9 @@ namespace sphrt {
 // two grid of the caller's scale record and added as two 64-bit integer atomics into a
 // {lo, hi} pair per voxel (fixed.hpp): integer sums, so the result is bitwise independent of the
 // order of the adds.  out (NORMAL_FIXED) is the same float64 forward.
+// What a mode does with a ray's segments is written twice, once per way of holding them:
+// consume_list for a wave with the compacted list in LDS (trace_one, exact_walk_wave), exact_walk
+// for the one lane that streams a sorted list from the workspace.
 enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4,
        MODE_SCATTER = 5, MODE_NORMAL = 6, MODE_SCATTER_FIXED = 7, MODE_NORMAL_FIXED = 8 };
 constexpr bool mode_scatter(int m) { return m == MODE_SCATTER || m == MODE_SCATTER_FIXED; }
@@ -493,59 +497,82 @@ __device__ __forceinline__ int64_t emit_slot(const TraceOut<T>& o, int64_t ray, 
     return -1;
 }
 
-// SCATTER: a ray's compacted segments (seg_vox, seg_len: nseg of them, in LDS) and its head
-// segment (hlen in voxel hvox, when `head`) added into the accumulator by the whole wave — every
-// channel's y[c][ray] (static, multichannel), or y[ray] into time slice ray / ray_chan_div.
-template <int MODE, typename T>
-__device__ __forceinline__ void scatter_segments(const TraceOut<T>& o, int64_t ray, int lane,
-                                                 int nseg, const int32_t* seg_vox,
-                                                 const double* seg_len, bool head, int hvox,
-                                                 double hlen) {
-    const FixedAdd fx = fixed_add_of<MODE>(o);
-    if (!fx.live) return;
-    int64_t c_lo = 0, c_hi = o.n_chan;
+// The channels ray `ray` touches, [lo, hi): all n_chan of a static multichannel density, or the one
+// time slice ray / ray_chan_div of a time-paired one.
+struct ChanRange {
+    int64_t lo, hi;
+};
+template <typename T>
+__device__ __forceinline__ ChanRange chan_range(const TraceOut<T>& o, int64_t ray) {
     if (o.ray_chan_div > 0) {
-        c_lo = ray / o.ray_chan_div;
-        c_hi = c_lo + 1;
+        const int64_t c = ray / o.ray_chan_div;
+        return {c, c + 1};
     }
-    for (int64_t c = c_lo; c < c_hi; ++c) {
-        const int64_t yc = o.ray_chan_div > 0 ? 0 : c;
-        const double yv = (double)o.density[yc * o.out_chan_stride + ray];
-        double* acc = o.acc + (mode_fixed(MODE) ? 2 : 1) * c * o.chan_stride;
-        if (head && lane == 0) acc_add<MODE>(acc, hvox, yv * hlen, fx);
-        for (int q = lane; q < nseg; q += 64) acc_add<MODE>(acc, seg_vox[q], yv * seg_len[q], fx);
-    }
+    return {0, o.n_chan};
+}
+// Where channel c of ray `ray` lies in the per-ray arrays (out, meas, SCATTER's y): channels
+// out_chan_stride apart; a time-paired ray has one value, its slice's.
+template <typename T>
+__device__ __forceinline__ int64_t ray_index(const TraceOut<T>& o, int64_t c, int64_t ray) {
+    return (o.ray_chan_div > 0 ? 0 : c) * o.out_chan_stride + ray;
 }
 
-// NORMAL: the same list integrated and scattered by the whole wave, channel by channel (the
-// channels of INTEGRATE).  The sum is MODE_INTEGRATE's — head segment on lane 0, strided lanes,
-// wave_sum, the same products in the same order — and goes to out; every lane then holds it and
-// forms the residual r = (sum - m) * scale (two roundings, sphrt_sq_residual_f64's), which is
-// scattered as SCATTER scatters y.
+// The segment sink: what every wave-level path does with a ray's list once it is compacted —
+// (seg_vox, seg_len), nseg of them in LDS, and the head segment (hlen in voxel hvox, when `head`).
+//   COUNT        the count.
+//   FILL / EMIT  the list copied to the CSR at r0 (the caller's row_ptr[ray] or emit_slot(); none
+//                when r0 < 0); `stored`: only the head is missing, the list is in place already.
+//   the rest     one channel loop of up to three parts.  The sum (INTEGRATE, NORMAL): head segment
+//                on lane 0, strided lanes, wave_sum — one order of products and adds, so NORMAL's
+//                out is bitwise INTEGRATE's.  The write of out, by lane 0.  The scatter (SCATTER,
+//                NORMAL): acc[c][vox] += w * len, one acc_add per segment, with w the ray's y
+//                (SCATTER) or the residual (sum - m) * scale (NORMAL; wave_sum leaves the sum in
+//                every lane; two roundings, sphrt_sq_residual_f64's).
 template <int MODE, typename T>
-__device__ __forceinline__ void normal_segments(const TraceOut<T>& o, int64_t ray, int lane,
-                                                int nseg, const int32_t* seg_vox,
-                                                const double* seg_len, bool head, int hvox,
-                                                double hlen) {
-    const FixedAdd fx = fixed_add_of<MODE>(o);
-    int64_t c_lo = 0, c_hi = o.n_chan;
-    if (o.ray_chan_div > 0) {
-        c_lo = ray / o.ray_chan_div;
-        c_hi = c_lo + 1;
-    }
-    for (int64_t c = c_lo; c < c_hi; ++c) {
-        const T* rho = o.density + c * o.chan_stride;
-        double sum = 0.0;
-        if (head && lane == 0) sum = (double)rho[hvox] * hlen;
-        for (int q = lane; q < nseg; q += 64) sum += (double)rho[seg_vox[q]] * seg_len[q];
-        sum = wave_sum(sum);
-        const int64_t oc = (o.ray_chan_div > 0) ? 0 : c;
-        if (lane == 0) o.out[oc * o.out_chan_stride + ray] = (T)sum;
-        const double r = (sum - o.meas[oc * o.out_chan_stride + ray]) * o.scale;
-        if (!fx.live) continue;
-        double* acc = o.acc + (mode_fixed(MODE) ? 2 : 1) * c * o.chan_stride;
-        if (head && lane == 0) acc_add<MODE>(acc, hvox, r * hlen, fx);
-        for (int q = lane; q < nseg; q += 64) acc_add<MODE>(acc, seg_vox[q], r * seg_len[q], fx);
+__device__ __forceinline__ void consume_list(const TraceOut<T>& o, int64_t ray, int lane, int nseg,
+                                             const int32_t* seg_vox, const double* seg_len,
+                                             bool head, int hvox, double hlen, int64_t r0 = 0,
+                                             bool stored = false) {
+    if constexpr (MODE == MODE_COUNT) {
+        if (lane == 0) o.counts[ray] = (head ? 1 : 0) + nseg;
+    } else if constexpr (MODE == MODE_FILL || MODE == MODE_EMIT) {
+        if (r0 < 0) return;
+        if (head && lane == 0) {
+            o.vox[r0] = hvox;
+            o.len[r0] = hlen;
+        }
+        const int64_t l0 = r0 + (head ? 1 : 0);
+        for (int q = lane; !stored && q < nseg; q += 64) {
+            o.vox[l0 + q] = seg_vox[q];
+            o.len[l0 + q] = seg_len[q];
+        }
+    } else {
+        constexpr bool kSum = MODE == MODE_INTEGRATE || mode_normal(MODE);
+        constexpr bool kScatter = mode_scatter(MODE) || mode_normal(MODE);
+        const FixedAdd fx = fixed_add_of<MODE>(o);
+        if (!kSum && !fx.live) return;
+        const ChanRange ch = chan_range(o, ray);
+        for (int64_t c = ch.lo; c < ch.hi; ++c) {
+            const int64_t rc = ray_index(o, c, ray);
+            double w = 0.0;   // what the scatter weighs the lengths with
+            if constexpr (kSum) {
+                const T* rho = o.density + c * o.chan_stride;
+                double sum = 0.0;
+                if (head && lane == 0) sum = (double)rho[hvox] * hlen;
+                for (int q = lane; q < nseg; q += 64) sum += (double)rho[seg_vox[q]] * seg_len[q];
+                sum = wave_sum(sum);
+                if (lane == 0) o.out[rc] = (T)sum;
+                if constexpr (kScatter) w = (sum - o.meas[rc]) * o.scale;
+            } else {
+                w = (double)o.density[rc];
+            }
+            if constexpr (kScatter) {
+                if (!fx.live) continue;
+                double* acc = o.acc + (mode_fixed(MODE) ? 2 : 1) * c * o.chan_stride;
+                if (head && lane == 0) acc_add<MODE>(acc, hvox, w * hlen, fx);
+                for (int q = lane; q < nseg; q += 64) acc_add<MODE>(acc, seg_vox[q], w * seg_len[q], fx);
+            }
+        }
     }
 }
 
@@ -1099,47 +1126,11 @@ __device__ void trace_one(const GridDev& G, const RayGeo& g, const double t1c_o,
     }
 
     // ---- 4. emit ---------------------------------------------------------------------------
-    if (MODE == MODE_COUNT) {
-        if (lane == 0) o.counts[ray] = head + nseg;
-    } else if (MODE == MODE_FILL || MODE == MODE_EMIT) {
-        const int64_t r0 = MODE == MODE_FILL ? slot0
-                                             : emit_slot(o, ray, head + nseg, lane == 0, slot0,
-                                                         slot1);
-        if (r0 < 0) {
-            wave_sync();
-            return;
-        }
-        if (head && lane == 0) {
-            o.vox[r0] = (sr * G.ne + se) * G.na + sa;
-            o.len[r0] = -tneg;
-        }
-        for (int q = lane; pair_fmt && q < nseg; q += 64) {    // (register lists stored already)
-            o.vox[r0 + head + q] = seg_vox[q];
-            o.len[r0 + head + q] = seg_len[q];
-        }
-    } else if (mode_scatter(MODE)) {
-        scatter_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
-                         (sr * G.ne + se) * G.na + sa, -tneg);
-    } else if (mode_normal(MODE)) {
-        normal_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
-                        (sr * G.ne + se) * G.na + sa, -tneg);
-    } else {
-        const int svox = (sr * G.ne + se) * G.na + sa;
-        int64_t c_lo = 0, c_hi = o.n_chan;
-        if (o.ray_chan_div > 0) {
-            c_lo = ray / o.ray_chan_div;
-            c_hi = c_lo + 1;
-        }
-        for (int64_t c = c_lo; c < c_hi; ++c) {
-            const T* rho = o.density + c * o.chan_stride;
-            double acc = 0.0;
-            if (head && lane == 0) acc = (double)rho[svox] * (-tneg);
-            for (int q = lane; q < nseg; q += 64) acc += (double)rho[seg_vox[q]] * seg_len[q];
-            acc = wave_sum(acc);
-            const int64_t oc = (o.ray_chan_div > 0) ? 0 : c;
-            if (lane == 0) o.out[oc * o.out_chan_stride + ray] = (T)acc;
-        }
-    }
+    int64_t r0 = slot0;
+    if constexpr (MODE == MODE_EMIT) r0 = emit_slot(o, ray, head + nseg, lane == 0, slot0, slot1);
+    // (FILL / EMIT lists in registers are in the CSR already)
+    consume_list<MODE>(o, ray, lane, nseg, seg_vox, seg_len, head != 0,
+                       (sr * G.ne + se) * G.na + sa, -tneg, r0, !pair_fmt);
     wave_sync();
 }
 
@@ -1486,82 +1477,85 @@ __device__ __forceinline__ int seg_voxel(const GridDev& G, int r, int e, int a) 
     return (r * G.ne + e) * G.na + a;
 }
 
-// Forward fill + diff + masking over the sorted list (raytracer.py:126, 140-173), one lane.
+// Forward fill + diff + masking over the sorted list (raytracer.py:126, 140-173), one lane:
+// seg(i, voxel, length) for the i-th kept segment, in order; returns their number.
+template <typename F, bool INV, class V, class Seg>
+__device__ __forceinline__ int64_t walk_list(const GridDev& G, const int* s, const V& v, Seg seg) {
+    const int K = G.K, r_lim = 2 * G.nbr, e_lim = 2 * G.nbr + 2 * G.nbe;
+    int cr = s[0], ce = s[1], ca = s[2];
+    int64_t nseg = 0;
+    auto cur = v.get(0);
+    for (int k = 0; k < K; ++k) {
+        const double t = cur.t;
+        const uint32_t p = cur.pay;
+        if (!(t < 0.0)) {
+            const int cand = (int)(p >> 16);
+            const int reg = (int)(p & 0xffffu) - 2;
+            if (cand == K - 1) { cr = s[0]; ce = s[1]; ca = s[2]; }
+            else if (cand < r_lim) cr = reg;
+            else if (cand < e_lim) { if (reg != -2) ce = reg; }
+            else if (reg != -2) ca = reg;
+        }
+        if (k + 1 < K) cur = v.get(k + 1);
+        const double tn = k + 1 < K ? cur.t : kInf;
+        const double len = seg_length<F>(tn, t);
+        if (!seg_keep<INV>(G, len, cr, ce, ca)) continue;
+        seg(nseg, seg_voxel<INV>(G, cr, ce, ca), len);
+        ++nseg;
+    }
+    return nseg;
+}
+
+// What the lane-serial exact path does with a ray's list, which it streams and cannot re-read
+// but by walking again.  The sum (INTEGRATE, NORMAL) walks once per channel and writes out; the
+// scatter (SCATTER, NORMAL) walks once, every channel per segment — NORMAL's after its sums,
+// forming the residuals from the out this lane just wrote.
 template <int MODE, typename T, typename F, bool INV, class V>
 __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, const int* s,
                            const V& v) {
-    const int K = G.K, r_lim = 2 * G.nbr, e_lim = 2 * G.nbr + 2 * G.nbe;
-    // NORMAL: INTEGRATE's walks (one per channel, each writing out), then one more (scat) that
-    // scatters the residuals of what this lane just wrote
-    constexpr bool kSum = MODE == MODE_INTEGRATE || mode_normal(MODE);
-    const FixedAdd fx = fixed_add_of<MODE>(o);   // (read once per ray, not per segment)
-    int64_t c_lo = 0, c_hi = o.n_chan;
-    if (kSum && o.ray_chan_div > 0) {
-        c_lo = ray / o.ray_chan_div;
-        c_hi = c_lo + 1;
-    }
-    if (!kSum) c_hi = c_lo + 1;
-    const int64_t c_end = mode_normal(MODE) ? c_hi + 1 : c_hi;
-    for (int64_t c = c_lo; c < c_end; ++c) {
-        const bool scat = mode_normal(MODE) && c == c_hi;
-        int cr = s[0], ce = s[1], ca = s[2];
-        int64_t nseg = 0;
-        double acc = 0.0;
-        const int64_t base = MODE == MODE_FILL || MODE == MODE_EMIT ? o.row_ptr[ray] : 0;
+    auto walk = [&](auto seg) { return walk_list<F, INV>(G, s, v, seg); };
+    if constexpr (MODE == MODE_COUNT) {
+        o.counts[ray] = (int32_t)walk([](int64_t, int, double) {});
+    } else if constexpr (MODE == MODE_FILL || MODE == MODE_EMIT) {
+        const int64_t base = o.row_ptr[ray];
         const int64_t cap = MODE == MODE_EMIT ? o.row_ptr[ray + 1] - base : INT64_MAX;
-        auto cur = v.get(0);
-        for (int k = 0; k < K; ++k) {
-            const double t = cur.t;
-            const uint32_t p = cur.pay;
-            if (!(t < 0.0)) {
-                const int cand = (int)(p >> 16);
-                const int reg = (int)(p & 0xffffu) - 2;
-                if (cand == K - 1) { cr = s[0]; ce = s[1]; ca = s[2]; }
-                else if (cand < r_lim) cr = reg;
-                else if (cand < e_lim) { if (reg != -2) ce = reg; }
-                else if (reg != -2) ca = reg;
+        const int64_t nseg = walk([&](int64_t i, int vx, double len) {
+            if (i < cap) {
+                o.vox[base + i] = vx;
+                o.len[base + i] = len;
             }
-            if (k + 1 < K) cur = v.get(k + 1);
-            const double tn = k + 1 < K ? cur.t : kInf;
-            const double len = seg_length<F>(tn, t);
-            if (!seg_keep<INV>(G, len, cr, ce, ca)) continue;
-            const int vx = seg_voxel<INV>(G, cr, ce, ca);
-            if (MODE == MODE_FILL || (MODE == MODE_EMIT && nseg < cap)) {
-                o.vox[base + nseg] = vx;
-                o.len[base + nseg] = len;
-            } else if (kSum && !scat) {
-                acc += (double)o.density[c * o.chan_stride + vx] * len;
-            } else if (mode_normal(MODE)) {
-                for (int64_t ch = c_lo; fx.live && ch < c_hi; ++ch) {
-                    const int64_t oc = (o.ray_chan_div > 0 ? 0 : ch) * o.out_chan_stride + ray;
-                    const double r = ((double)o.out[oc] - o.meas[oc]) * o.scale;
-                    acc_add<MODE>(o.acc, ch * o.chan_stride + vx, r * len, fx);
-                }
-            } else if (mode_scatter(MODE)) {   // (one walk: every channel per segment)
-                if (!fx.live) {
-                } else if (o.ray_chan_div > 0) {
-                    acc_add<MODE>(o.acc, (ray / o.ray_chan_div) * o.chan_stride + vx,
-                                  (double)o.density[ray] * len, fx);
-                } else {
-                    for (int64_t ch = 0; ch < o.n_chan; ++ch)
-                        acc_add<MODE>(o.acc, ch * o.chan_stride + vx,
-                                      (double)o.density[ch * o.out_chan_stride + ray] * len, fx);
-                }
-            }
-            ++nseg;
-        }
-        if (MODE == MODE_COUNT) o.counts[ray] = (int32_t)nseg;
+        });
         if (MODE == MODE_EMIT) (void)emit_slot(o, ray, nseg, true);
-        if (kSum && !scat) {
-            const int64_t oc = o.ray_chan_div > 0 ? 0 : c;
-            o.out[oc * o.out_chan_stride + ray] = (T)acc;
+    } else {
+        const FixedAdd fx = fixed_add_of<MODE>(o);   // (read once per ray, not per segment)
+        const ChanRange ch = chan_range(o, ray);
+        if constexpr (MODE == MODE_INTEGRATE || mode_normal(MODE)) {
+            for (int64_t c = ch.lo; c < ch.hi; ++c) {
+                double acc = 0.0;
+                walk([&](int64_t, int vx, double len) {
+                    acc += (double)o.density[c * o.chan_stride + vx] * len;
+                });
+                o.out[ray_index(o, c, ray)] = (T)acc;
+            }
+        }
+        if constexpr (MODE != MODE_INTEGRATE) {
+            if (!fx.live) return;
+            walk([&](int64_t, int vx, double len) {
+                for (int64_t c = ch.lo; c < ch.hi; ++c) {
+                    const int64_t rc = ray_index(o, c, ray);
+                    double w;                                  // the residual, or y
+                    if constexpr (mode_normal(MODE)) w = ((double)o.out[rc] - o.meas[rc]) * o.scale;
+                    else w = (double)o.density[rc];
+                    acc_add<MODE>(o.acc, c * o.chan_stride + vx, w * len, fx);
+                }
+            });
         }
     }
 }
 
 // The same walk, wave-parallel over 64-entry chunks of the sorted list (ts, ps): "last update
 // wins" scans for the three region rows, differences, and in-order compaction of the non-zero
-// in-grid segments into (seg_vox, seg_len) (LDS, K entries), then count / copy / integrate.
+// in-grid segments into (seg_vox, seg_len) (LDS, K entries), which go to consume_list.
 template <int MODE, typename T, typename F, bool INV>
 __device__ void exact_walk_wave(const GridDev& G, const TraceOut<T>& o, int64_t ray, const int* s,
                                 const double* ts, const uint32_t* ps, int32_t* seg_vox,
@@ -1609,33 +1603,10 @@ __device__ void exact_walk_wave(const GridDev& G, const TraceOut<T>& o, int64_t 
         nseg += __popcll(m);
     }
     wave_sync();
-    if (MODE == MODE_COUNT) {
-        if (lane == 0) o.counts[ray] = nseg;
-    } else if (MODE == MODE_FILL || MODE == MODE_EMIT) {
-        const int64_t r0 = MODE == MODE_FILL ? o.row_ptr[ray] : emit_slot(o, ray, nseg, lane == 0);
-        for (int q = lane; r0 >= 0 && q < nseg; q += 64) {
-            o.vox[r0 + q] = seg_vox[q];
-            o.len[r0 + q] = seg_len[q];
-        }
-    } else if (mode_scatter(MODE)) {
-        scatter_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
-    } else if (mode_normal(MODE)) {
-        normal_segments<MODE>(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0);
-    } else {
-        int64_t c_lo = 0, c_hi = o.n_chan;
-        if (o.ray_chan_div > 0) {
-            c_lo = ray / o.ray_chan_div;
-            c_hi = c_lo + 1;
-        }
-        for (int64_t c = c_lo; c < c_hi; ++c) {
-            const T* rho = o.density + c * o.chan_stride;
-            double acc = 0.0;
-            for (int q = lane; q < nseg; q += 64) acc += (double)rho[seg_vox[q]] * seg_len[q];
-            acc = wave_sum(acc);
-            const int64_t oc = (o.ray_chan_div > 0) ? 0 : c;
-            if (lane == 0) o.out[oc * o.out_chan_stride + ray] = (T)acc;
-        }
-    }
+    int64_t r0 = 0;
+    if constexpr (MODE == MODE_FILL) r0 = o.row_ptr[ray];
+    if constexpr (MODE == MODE_EMIT) r0 = emit_slot(o, ray, nseg, lane == 0);
+    consume_list<MODE>(o, ray, lane, nseg, seg_vox, seg_len, false, 0, 0.0, r0);
 }
 
 // Large K (the wave list does not fit kExactLdsMax): lane 0 sorts the ray's list serially in the
@@ -2151,10 +2122,50 @@ static bool exact_multi_wave(const GridDev& G) {
 static size_t exact_scratch_bytes(const GridDev& G) {   // lists of large-K grids, one per wave
     return exact_in_lds(G) ? 0 : (size_t)kExactSerialBlocks * G.K * sizeof(Cand);
 }
-static size_t hits_bytes(int64_t n) { return (((size_t)n * sizeof(HitRay) + 255) / 256) * 256; }
+// The trace workspace, carved in one place: the counters (deferred rays at 0, hit rays at 64,
+// heap ranges at 128), then the deferred ray ids, the hit records and the serial exact kernel's
+// lists, each rounded to 256 B.  base may be null: only `bytes` is then meaningful.
+struct Workspace {
+    size_t bytes;
+    unsigned long long* n_deferred;
+    unsigned* n_hits;
+    unsigned long long* n_heap;
+    int64_t* deferred;
+    HitRay* hits;
+    Cand* scratch;
+};
+static Workspace carve_workspace(const GridDev& G, int64_t n, void* base) {
+    auto round256 = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t ids = kWsHead, hits = ids + round256((size_t)n * sizeof(int64_t)),
+                 scratch = hits + round256((size_t)n * sizeof(HitRay));
+    Workspace w{};
+    w.bytes = scratch + exact_scratch_bytes(G);
+    if (unsigned char* p = (unsigned char*)base) {
+        w.n_deferred = (unsigned long long*)p;
+        w.n_hits = (unsigned*)(p + 64);
+        w.n_heap = (unsigned long long*)(p + 128);
+        w.deferred = (int64_t*)(p + ids);
+        w.hits = (HitRay*)(p + hits);
+        w.scratch = (Cand*)(p + scratch);
+    }
+    return w;
+}
 static size_t workspace_bytes(const GridDev& G, int64_t n) {
-    return kWsHead + (((size_t)n * sizeof(int64_t) + 255) / 256) * 256 + hits_bytes(n) +
-           exact_scratch_bytes(G);
+    return carve_workspace(G, n, nullptr).bytes;
+}
+static int refuse_workspace(const GridDev& G, int64_t n, void* workspace, size_t workspace_size) {
+    if (n > 0 && (!workspace || workspace_size < workspace_bytes(G, n)))
+        return fail("trace workspace too small: %zu < %zu bytes", workspace_size,
+                    workspace_bytes(G, n));
+    return 0;
+}
+// What every trace launcher checks first, and the carved workspace (R.n == 0: nothing to launch).
+static int open_trace(const GridDev& G, const RaysDev& R, void* workspace, size_t workspace_size,
+                      Workspace& ws) {
+    if (G.nr < 1 || G.ne < 1 || G.na < 1) return fail("tracing needs at least one voxel per axis");
+    if (int e = refuse_workspace(G, R.n, workspace, workspace_size)) return e;
+    ws = carve_workspace(G, R.n, workspace);
+    return 0;
 }
 
 // The half-plane wedge (trace_one) is on unless SPHRT_TRACE_WEDGE=0 (A/B tests: the CSR is the
@@ -2164,19 +2175,15 @@ static bool wedge_enabled() {
     return !(e && e[0] == '0');
 }
 
-// Which launches of a trace a call makes: screen (hit list; counts/zeros/bounds of the misses)
-// and trace (the hit rays + the deferred exact ones).  BOUND screens only; EMIT traces the hit
-// list an earlier BOUND call left in the same workspace.
-enum { kScreen = 1, kTrace = 2 };
-
+// A trace launches the screen (hit list; counts/zeros/bounds of the misses) and the trace (the
+// hit rays + the deferred exact ones).  BOUND screens only; EMIT traces the hit list an earlier
+// BOUND call left in the same workspace.
 template <int MODE, typename T>
 static int launch_trace(const GridDev& G, const RaysDev& R, TraceOut<T> o, void* workspace,
-                        size_t workspace_size, hipStream_t st, int steps = kScreen | kTrace) {
-    if (G.nr < 1 || G.ne < 1 || G.na < 1) return fail("tracing needs at least one voxel per axis");
+                        size_t workspace_size, hipStream_t st) {
+    Workspace ws;
+    if (int e = open_trace(G, R, workspace, workspace_size, ws)) return e;
     if (R.n == 0) return 0;
-    if (!workspace || workspace_size < workspace_bytes(G, R.n))
-        return fail("trace workspace too small: %zu < %zu bytes", workspace_size,
-                    workspace_bytes(G, R.n));
     const int cap = trace_cap(G);
     // one LDS list of K entries per wave: 4 waves per workgroup, fewer for large K (a workgroup
     // may hold all 160 KiB of a CU's LDS), K <= 13653 with one wave; larger K (e.g. ~6800+
@@ -2186,18 +2193,14 @@ static int launch_trace(const GridDev& G, const RaysDev& R, TraceOut<T> o, void*
     while (waves > 1 && (size_t)waves * per_wave > kLdsBytes) waves >>= 1;
     const size_t lds = (size_t)waves * per_wave;
     const bool wave_list = lds <= kLdsBytes;
-    unsigned char* ws = (unsigned char*)workspace;
-    o.n_deferred = (unsigned long long*)ws;
-    o.n_hits = (unsigned*)(ws + 64);
-    o.n_heap = (unsigned long long*)(ws + 128);
-    o.deferred = (int64_t*)(ws + kWsHead);
-    o.hits = (HitRay*)(ws + kWsHead + (((size_t)R.n * sizeof(int64_t) + 255) / 256) * 256);
+    o.n_deferred = ws.n_deferred;
+    o.n_hits = ws.n_hits;
+    o.n_heap = ws.n_heap;
+    o.deferred = ws.deferred;
+    o.hits = ws.hits;
     o.wedge = wedge_enabled();
-    Cand* scratch = (Cand*)(ws + workspace_bytes(G, R.n) - exact_scratch_bytes(G));
-    if constexpr (MODE == MODE_BOUND) steps = kScreen;
-    if constexpr (MODE == MODE_EMIT) steps = kTrace;
-    if (steps & kScreen) {
-        if (hipMemsetAsync(ws, 0, kWsHead, st) != hipSuccess) return fail("memset failed");
+    if (MODE != MODE_EMIT) {
+        if (hipMemsetAsync(workspace, 0, kWsHead, st) != hipSuccess) return fail("memset failed");
         const size_t slds = MODE == MODE_BOUND && screen_lds(G)
                                 ? (size_t)(G.nbr + G.nbe + G.nba) * sizeof(double) : 0;
         hipLaunchKernelGGL((screen_kernel<MODE, T>), dim3((unsigned)((R.n + 255) / 256)), dim3(256),
@@ -2207,7 +2210,6 @@ static int launch_trace(const GridDev& G, const RaysDev& R, TraceOut<T> o, void*
         return fail("memset failed");
     }
     if constexpr (MODE == MODE_BOUND) return 0;
-    if (!(steps & kTrace)) return 0;
     if (wave_list) {
         // enough waves to fill the chip several times over; each drains hits[w], hits[w + W], ...
         const int64_t grid = kTraceGrid * kWavesPerBlock / waves;
@@ -2227,7 +2229,7 @@ static int launch_trace(const GridDev& G, const RaysDev& R, TraceOut<T> o, void*
                            exact_wave_lds(G.K, 1), st, G, R, o);
     else
         hipLaunchKernelGGL((exact_kernel<MODE, T>), dim3(kExactSerialBlocks), dim3(64), 0, st, G, R, o,
-                           scratch);
+                           ws.scratch);
     return check_launch("exact_kernel");
 }
 
@@ -2241,49 +2243,56 @@ extern "C" size_t sphrt_trace_workspace_bytes(const sphrt_plan* plan, int64_t n)
     return workspace_bytes(plan->dev, n);
 }
 
-extern "C" int sphrt_trace_count(const sphrt_plan* plan, const sphrt_rays* rays, int32_t* counts,
-                                 void* workspace, size_t workspace_size, void* stream) {
+// Every traced entry's way in: the plan and rays resolved on the stream's device, the entry's own
+// argument refusal (its message, null when there is none: it follows resolve's), the launch.
+template <int MODE, typename T>
+static int run_trace(const sphrt_plan* plan, const sphrt_rays* rays, const char* refusal,
+                     const TraceOut<T>& o, void* workspace, size_t workspace_size, void* stream) {
     GridDev G;
     RaysDev R;
     if (int e = resolve(plan, rays, G, R, stream)) return e;
     DeviceGuard guard(plan->device);
+    if (refusal) return fail("%s", refusal);
+    hipStream_t st = (hipStream_t)stream;
+    if (MODE == MODE_EMIT && hipMemsetAsync(o.n_over, 0, sizeof(int64_t), st) != hipSuccess)
+        return fail("memset failed");
+    return launch_trace<MODE, T>(G, R, o, workspace, workspace_size, st);
+}
+
+// The CSR a trace writes: per-ray counts (COUNT; BOUND: the bounds), rows at row_ptr (FILL) or in
+// the slots row_ptr bounds (EMIT, with its counter of the rays that did not fit).
+static TraceOut<double> csr_out(int32_t* counts, const int64_t* row_ptr, int32_t* vox, double* len,
+                                int64_t* n_over = nullptr) {
     TraceOut<double> o{};
     o.counts = counts;
-    return launch_trace<MODE_COUNT, double>(G, R, o, workspace, workspace_size,
-                                            (hipStream_t)stream);
+    o.row_ptr = row_ptr;
+    o.vox = vox;
+    o.len = len;
+    o.n_over = (unsigned long long*)n_over;
+    return o;
+}
+
+extern "C" int sphrt_trace_count(const sphrt_plan* plan, const sphrt_rays* rays, int32_t* counts,
+                                 void* workspace, size_t workspace_size, void* stream) {
+    return run_trace<MODE_COUNT>(plan, rays, nullptr, csr_out(counts, nullptr, nullptr, nullptr),
+                                 workspace, workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_bound(const sphrt_plan* plan, const sphrt_rays* rays, int32_t* bounds,
                                  void* workspace, size_t workspace_size, void* stream) {
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    if (!bounds) return fail("null bounds");
-    TraceOut<double> o{};
-    o.counts = bounds;
-    return launch_trace<MODE_BOUND, double>(G, R, o, workspace, workspace_size,
-                                            (hipStream_t)stream, kScreen);
+    return run_trace<MODE_BOUND>(plan, rays, bounds ? nullptr : "null bounds",
+                                 csr_out(bounds, nullptr, nullptr, nullptr), workspace,
+                                 workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_emit(const sphrt_plan* plan, const sphrt_rays* rays,
                                 const int64_t* bound_ptr, int32_t* counts, int32_t* svox,
                                 double* slen, int64_t* n_over, void* workspace,
                                 size_t workspace_size, void* stream) {
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    if (!bound_ptr || !counts || !svox || !slen || !n_over) return fail("null emit argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(n_over, 0, sizeof(int64_t), st) != hipSuccess) return fail("memset failed");
-    TraceOut<double> o{};
-    o.row_ptr = bound_ptr;
-    o.counts = counts;
-    o.vox = svox;
-    o.len = slen;
-    o.n_over = (unsigned long long*)n_over;
-    return launch_trace<MODE_EMIT, double>(G, R, o, workspace, workspace_size, st, kTrace);
+    const bool null_arg = !bound_ptr || !counts || !svox || !slen || !n_over;
+    return run_trace<MODE_EMIT>(plan, rays, null_arg ? "null emit argument" : nullptr,
+                                csr_out(counts, bound_ptr, svox, slen, n_over), workspace,
+                                workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_compact(int64_t n, const int64_t* bound_ptr, const int32_t* svox,
@@ -2305,38 +2314,35 @@ extern "C" int sphrt_trace_compact(int64_t n, const int64_t* bound_ptr, const in
 extern "C" int sphrt_trace_fill(const sphrt_plan* plan, const sphrt_rays* rays,
                                 const int64_t* row_ptr, int32_t* vox, double* len,
                                 void* workspace, size_t workspace_size, void* stream) {
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    TraceOut<double> o{};
-    o.row_ptr = row_ptr;
-    o.vox = vox;
-    o.len = len;
-    return launch_trace<MODE_FILL, double>(G, R, o, workspace, workspace_size,
-                                           (hipStream_t)stream);
+    return run_trace<MODE_FILL>(plan, rays, nullptr, csr_out(nullptr, row_ptr, vox, len),
+                                workspace, workspace_size, stream);
 }
 
+// The fused modes' TraceOut.  `in` is the density (INTEGRATE, NORMAL) or y (SCATTER); ray_stride
+// lies between the channels of the per-ray arrays (out, m, y), chan_stride between those of the
+// per-voxel ones (density, acc).  acc: float64, or with a scale record the int64 {lo, hi} pairs.
 template <typename T>
-static int trace_integrate(const sphrt_plan* plan, const sphrt_rays* rays, const T* density,
-                           int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div, T* out,
-                           int64_t out_chan_stride, void* workspace, size_t workspace_size,
-                           void* stream) {
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    if (n_chan < 1) return fail("n_chan must be >= 1");
-    if (ray_chan_div > 0 && n_chan != 1) return fail("ray_chan_div requires n_chan == 1");
+static TraceOut<T> fused_out(const T* in, int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+                             T* out, int64_t ray_stride, void* acc = nullptr,
+                             const double* m = nullptr, double scale = 0.0,
+                             const void* scale_rec = nullptr) {
     TraceOut<T> o{};
-    o.density = density;
+    o.density = in;
     o.n_chan = n_chan;
     o.chan_stride = chan_stride;
     o.ray_chan_div = ray_chan_div;
     o.out = out;
-    o.out_chan_stride = out_chan_stride;
-    return launch_trace<MODE_INTEGRATE, T>(G, R, o, workspace, workspace_size,
-                                           (hipStream_t)stream);
+    o.out_chan_stride = ray_stride;
+    o.acc = static_cast<double*>(acc);
+    o.meas = m;
+    o.scale = scale;
+    o.fixed_rec = static_cast<const int32_t*>(scale_rec);
+    return o;
+}
+static const char* refuse_channels(int64_t n_chan, int64_t ray_chan_div) {
+    if (n_chan < 1) return "n_chan must be >= 1";
+    if (ray_chan_div > 0 && n_chan != 1) return "ray_chan_div requires n_chan == 1";
+    return nullptr;
 }
 
 extern "C" int sphrt_trace_integrate_f32(const sphrt_plan* plan, const sphrt_rays* rays,
@@ -2344,16 +2350,33 @@ extern "C" int sphrt_trace_integrate_f32(const sphrt_plan* plan, const sphrt_ray
                                          int64_t chan_stride, int64_t ray_chan_div, float* out,
                                          int64_t out_chan_stride, void* workspace,
                                          size_t workspace_size, void* stream) {
-    return trace_integrate<float>(plan, rays, density, n_chan, chan_stride, ray_chan_div, out,
-                                  out_chan_stride, workspace, workspace_size, stream);
+    return run_trace<MODE_INTEGRATE>(
+        plan, rays, refuse_channels(n_chan, ray_chan_div),
+        fused_out(density, n_chan, chan_stride, ray_chan_div, out, out_chan_stride), workspace,
+        workspace_size, stream);
 }
 extern "C" int sphrt_trace_integrate_f64(const sphrt_plan* plan, const sphrt_rays* rays,
                                          const double* density, int64_t n_chan,
                                          int64_t chan_stride, int64_t ray_chan_div, double* out,
                                          int64_t out_chan_stride, void* workspace,
                                          size_t workspace_size, void* stream) {
-    return trace_integrate<double>(plan, rays, density, n_chan, chan_stride, ray_chan_div, out,
-                                   out_chan_stride, workspace, workspace_size, stream);
+    return run_trace<MODE_INTEGRATE>(
+        plan, rays, refuse_channels(n_chan, ray_chan_div),
+        fused_out(density, n_chan, chan_stride, ray_chan_div, out, out_chan_stride), workspace,
+        workspace_size, stream);
+}
+
+// The rays of a batch's shape, the product of its extents, in n; or why there is none.  kShapeCap:
+// an extent or the product so far (n) reached cap — n never exceeds it, whatever the extents.
+enum { kShapeOk = 0, kShapeRank, kShapeNegative, kShapeCap };
+static int ray_count(const sphrt_rays* rays, int64_t cap, int64_t& n) {
+    n = 1;
+    if (rays->ndim < 0 || rays->ndim > kMaxDims) return kShapeRank;
+    for (int d = 0; d < rays->ndim; ++d) {
+        if (rays->shape[d] < 0) return kShapeNegative;
+        if (rays->shape[d] >= cap || (n *= rays->shape[d]) >= cap) return kShapeCap;
+    }
+    return kShapeOk;
 }
 
 // The refusals the fused entries with an accumulator share (back-projection, normal), every one
@@ -2365,15 +2388,11 @@ static int refuse_fused(const sphrt_plan* plan, const sphrt_rays* rays, const ch
     if (!plan) return fail("null plan");
     if (!rays) return fail("null ray batch");
     if (null_arg) return fail("%s", null_arg);
-    if (n_chan < 1) return fail("n_chan must be >= 1");
-    if (ray_chan_div > 0 && n_chan != 1) return fail("ray_chan_div requires n_chan == 1");
-    if (rays->ndim < 0 || rays->ndim > kMaxDims)
-        return fail("ray batch rank %d out of range", rays->ndim);
-    int64_t n = 1;
-    for (int d = 0; d < rays->ndim; ++d) {
-        if (rays->shape[d] < 0) return fail("negative ray-batch extent");
-        n *= rays->shape[d];
-    }
+    if (const char* why = refuse_channels(n_chan, ray_chan_div)) return fail("%s", why);
+    int64_t n;
+    const int shape = ray_count(rays, INT64_MAX, n);
+    if (shape == kShapeRank) return fail("ray batch rank %d out of range", rays->ndim);
+    if (shape == kShapeNegative) return fail("negative ray-batch extent");
     const GridDev& P = plan->dev;
     if (chan_stride < (int64_t)P.nr * P.ne * P.na)
         return fail("chan_stride %lld is smaller than the grid's %lld voxels", (long long)chan_stride,
@@ -2381,34 +2400,79 @@ static int refuse_fused(const sphrt_plan* plan, const sphrt_rays* rays, const ch
     if (n_chan > 1 && y_chan_stride < n)
         return fail("y_chan_stride %lld is smaller than the %lld rays", (long long)y_chan_stride,
                     (long long)n);
-    if (n > 0 && (!workspace || workspace_size < workspace_bytes(P, n)))
-        return fail("trace workspace too small: %zu < %zu bytes", workspace_size,
-                    workspace_bytes(P, n));
+    return refuse_workspace(P, n, workspace, workspace_size);
+}
+
+// What the fixed-point entries refuse before refuse_fused, on the host: a null scale record, and
+// a batch that could exhaust a voxel's capacity of 2^31 adds (fixed.hpp) — every ray adds to a
+// voxel at most a few times per channel, so n_rays * n_chan < 2^29 keeps any number of such
+// calls a caller is likely to make into one accumulator below it.  A bad shape is left to
+// refuse_fused's message.
+constexpr int64_t kFixedBatchCap = (int64_t)1 << 29;
+static int refuse_fixed(const sphrt_plan* plan, const sphrt_rays* rays, int64_t n_chan,
+                        const void* scale_rec) {
+    if (!plan) return fail("null plan");
+    if (!rays) return fail("null ray batch");
+    if (!scale_rec) return fail("null scale record");
+    int64_t n;
+    const int shape = ray_count(rays, kFixedBatchCap, n);
+    if (shape == kShapeCap)
+        return fail("%lld or more rays exceed the fixed-point capacity of 2^29 adds per call",
+                    (long long)n);
+    if (shape != kShapeOk) return 0;
+    if (n * (n_chan > 1 ? n_chan : 1) >= kFixedBatchCap || n_chan >= kFixedBatchCap)
+        return fail("%lld rays x %lld channels exceed the fixed-point capacity of 2^29 adds per "
+                    "call", (long long)n, (long long)n_chan);
     return 0;
+}
+
+// Back-projection and normal, float64 atomics or (scale_rec) fixed point: the host refusals, then
+// the trace.
+template <int MODE>
+static int run_backproject(const sphrt_plan* plan, const sphrt_rays* rays, const double* y,
+                           int64_t n_chan, int64_t y_chan_stride, int64_t ray_chan_div, void* acc,
+                           int64_t chan_stride, const void* scale_rec, void* workspace,
+                           size_t workspace_size, void* stream) {
+    if constexpr (mode_fixed(MODE)) {
+        if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
+    }
+    if (int e = refuse_fused(plan, rays,
+                             !y || !acc ? "null back-projection argument (y or acc)" : nullptr,
+                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
+                             workspace_size))
+        return e;
+    return run_trace<MODE>(plan, rays, nullptr,
+                           fused_out<double>(y, n_chan, chan_stride, ray_chan_div, nullptr,
+                                             y_chan_stride, acc, nullptr, 0.0, scale_rec),
+                           workspace, workspace_size, stream);
+}
+template <int MODE>
+static int run_normal(const sphrt_plan* plan, const sphrt_rays* rays, const double* density,
+                      const double* m, double scale, int64_t n_chan, int64_t chan_stride,
+                      int64_t ray_chan_div, double* yhat, int64_t y_chan_stride, void* acc,
+                      const void* scale_rec, void* workspace, size_t workspace_size,
+                      void* stream) {
+    if constexpr (mode_fixed(MODE)) {
+        if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
+    }
+    if (int e = refuse_fused(plan, rays,
+                             !density || !m || !yhat || !acc
+                                 ? "null normal argument (density, m, yhat or acc)" : nullptr,
+                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
+                             workspace_size))
+        return e;
+    return run_trace<MODE>(plan, rays, nullptr,
+                           fused_out(density, n_chan, chan_stride, ray_chan_div, yhat,
+                                     y_chan_stride, acc, m, scale, scale_rec),
+                           workspace, workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_backproject_f64(const sphrt_plan* plan, const sphrt_rays* rays,
                                            const double* y, int64_t n_chan, int64_t y_chan_stride,
                                            int64_t ray_chan_div, double* acc, int64_t chan_stride,
                                            void* workspace, size_t workspace_size, void* stream) {
-    if (int e = refuse_fused(plan, rays,
-                             !y || !acc ? "null back-projection argument (y or acc)" : nullptr,
-                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
-                             workspace_size))
-        return e;
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    TraceOut<double> o{};
-    o.density = y;
-    o.n_chan = n_chan;
-    o.chan_stride = chan_stride;
-    o.ray_chan_div = ray_chan_div;
-    o.out_chan_stride = y_chan_stride;
-    o.acc = acc;
-    return launch_trace<MODE_SCATTER, double>(G, R, o, workspace, workspace_size,
-                                              (hipStream_t)stream);
+    return run_backproject<MODE_SCATTER>(plan, rays, y, n_chan, y_chan_stride, ray_chan_div, acc,
+                                         chan_stride, nullptr, workspace, workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_normal_f64(const sphrt_plan* plan, const sphrt_rays* rays,
@@ -2416,53 +2480,9 @@ extern "C" int sphrt_trace_normal_f64(const sphrt_plan* plan, const sphrt_rays* 
                                       int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
                                       double* yhat, int64_t y_chan_stride, double* acc,
                                       void* workspace, size_t workspace_size, void* stream) {
-    if (int e = refuse_fused(plan, rays,
-                             !density || !m || !yhat || !acc
-                                 ? "null normal argument (density, m, yhat or acc)" : nullptr,
-                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
-                             workspace_size))
-        return e;
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    TraceOut<double> o{};
-    o.density = density;
-    o.n_chan = n_chan;
-    o.chan_stride = chan_stride;
-    o.ray_chan_div = ray_chan_div;
-    o.out = yhat;
-    o.out_chan_stride = y_chan_stride;
-    o.acc = acc;
-    o.meas = m;
-    o.scale = scale;
-    return launch_trace<MODE_NORMAL, double>(G, R, o, workspace, workspace_size,
-                                             (hipStream_t)stream);
-}
-
-// What the fixed-point entries refuse on top of refuse_fused, on the host: a null scale record,
-// and a batch that could exhaust a voxel's capacity of 2^31 adds (fixed.hpp) — every ray adds to
-// a voxel at most a few times per channel, so n_rays * n_chan < 2^29 keeps any number of such
-// calls a caller is likely to make into one accumulator below it.
-constexpr int64_t kFixedBatchCap = (int64_t)1 << 29;
-static int refuse_fixed(const sphrt_plan* plan, const sphrt_rays* rays, int64_t n_chan,
-                        const void* scale_rec) {
-    if (!plan) return fail("null plan");
-    if (!rays) return fail("null ray batch");
-    if (!scale_rec) return fail("null scale record");
-    if (rays->ndim < 0 || rays->ndim > kMaxDims) return 0;     // (refuse_fused's message)
-    int64_t n = 1;
-    for (int d = 0; d < rays->ndim; ++d) {
-        if (rays->shape[d] < 0) return 0;
-        // (n stays below the cap: no overflow whatever the extents are)
-        if (rays->shape[d] >= kFixedBatchCap || (n *= rays->shape[d]) >= kFixedBatchCap)
-            return fail("%lld or more rays exceed the fixed-point capacity of 2^29 adds per call",
-                        (long long)n);
-    }
-    if (n * (n_chan > 1 ? n_chan : 1) >= kFixedBatchCap || n_chan >= kFixedBatchCap)
-        return fail("%lld rays x %lld channels exceed the fixed-point capacity of 2^29 adds per "
-                    "call", (long long)n, (long long)n_chan);
-    return 0;
+    return run_normal<MODE_NORMAL>(plan, rays, density, m, scale, n_chan, chan_stride,
+                                   ray_chan_div, yhat, y_chan_stride, acc, nullptr, workspace,
+                                   workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_backproject_fixed_f64(const sphrt_plan* plan, const sphrt_rays* rays,
@@ -2471,26 +2491,9 @@ extern "C" int sphrt_trace_backproject_fixed_f64(const sphrt_plan* plan, const s
                                                  int64_t* acc, int64_t chan_stride,
                                                  const void* scale_rec, void* workspace,
                                                  size_t workspace_size, void* stream) {
-    if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
-    if (int e = refuse_fused(plan, rays,
-                             !y || !acc ? "null back-projection argument (y or acc)" : nullptr,
-                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
-                             workspace_size))
-        return e;
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    TraceOut<double> o{};
-    o.density = y;
-    o.n_chan = n_chan;
-    o.chan_stride = chan_stride;
-    o.ray_chan_div = ray_chan_div;
-    o.out_chan_stride = y_chan_stride;
-    o.acc = reinterpret_cast<double*>(acc);
-    o.fixed_rec = static_cast<const int32_t*>(scale_rec);
-    return launch_trace<MODE_SCATTER_FIXED, double>(G, R, o, workspace, workspace_size,
-                                                    (hipStream_t)stream);
+    return run_backproject<MODE_SCATTER_FIXED>(plan, rays, y, n_chan, y_chan_stride, ray_chan_div,
+                                               acc, chan_stride, scale_rec, workspace,
+                                               workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_normal_fixed_f64(const sphrt_plan* plan, const sphrt_rays* rays,
@@ -2500,30 +2503,9 @@ extern "C" int sphrt_trace_normal_fixed_f64(const sphrt_plan* plan, const sphrt_
                                             int64_t y_chan_stride, int64_t* acc,
                                             const void* scale_rec, void* workspace,
                                             size_t workspace_size, void* stream) {
-    if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
-    if (int e = refuse_fused(plan, rays,
-                             !density || !m || !yhat || !acc
-                                 ? "null normal argument (density, m, yhat or acc)" : nullptr,
-                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
-                             workspace_size))
-        return e;
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    TraceOut<double> o{};
-    o.density = density;
-    o.n_chan = n_chan;
-    o.chan_stride = chan_stride;
-    o.ray_chan_div = ray_chan_div;
-    o.out = yhat;
-    o.out_chan_stride = y_chan_stride;
-    o.acc = reinterpret_cast<double*>(acc);
-    o.meas = m;
-    o.scale = scale;
-    o.fixed_rec = static_cast<const int32_t*>(scale_rec);
-    return launch_trace<MODE_NORMAL_FIXED, double>(G, R, o, workspace, workspace_size,
-                                                   (hipStream_t)stream);
+    return run_normal<MODE_NORMAL_FIXED>(plan, rays, density, m, scale, n_chan, chan_stride,
+                                         ray_chan_div, yhat, y_chan_stride, acc, scale_rec,
+                                         workspace, workspace_size, stream);
 }
 
 template <typename F>
@@ -2601,17 +2583,14 @@ __global__ __launch_bounds__(256) void ref_screen_kernel(GridDev G, RaysDev R, T
 template <int MODE, typename F, bool INV>
 static int launch_reference(const GridDev& G, const RaysDev& R, TraceOut<double> o,
                             void* workspace, size_t workspace_size, hipStream_t st) {
-    if (G.nr < 1 || G.ne < 1 || G.na < 1) return fail("tracing needs at least one voxel per axis");
+    Workspace ws;
+    if (int e = open_trace(G, R, workspace, workspace_size, ws)) return e;
     if (R.n == 0) return 0;
-    if (!workspace || workspace_size < workspace_bytes(G, R.n))
-        return fail("trace workspace too small: %zu < %zu bytes", workspace_size,
-                    workspace_bytes(G, R.n));
-    unsigned char* ws = (unsigned char*)workspace;
-    o.n_deferred = (unsigned long long*)ws;
-    o.n_heap = (unsigned long long*)(ws + 128);
-    if (hipMemsetAsync(ws, 0, kWsHead, st) != hipSuccess) return fail("memset failed");
+    o.n_deferred = ws.n_deferred;
+    o.n_heap = ws.n_heap;
+    if (hipMemsetAsync(workspace, 0, kWsHead, st) != hipSuccess) return fail("memset failed");
     if (!INV) {
-        o.deferred = (int64_t*)(ws + kWsHead);
+        o.deferred = ws.deferred;
         hipLaunchKernelGGL((ref_screen_kernel<MODE, F>), dim3((unsigned)((R.n + 255) / 256)),
                            dim3(256), 0, st, G, R, o);
         if (int e = check_launch("ref_screen_kernel")) return e;
@@ -2621,71 +2600,57 @@ static int launch_reference(const GridDev& G, const RaysDev& R, TraceOut<double>
         hipLaunchKernelGGL((exact_wave_kernel<MODE, double, F, INV, true>), dim3((unsigned)blocks),
                            dim3(64), exact_wave_lds(G.K, 1), st, G, R, o);
     } else {
-        Cand* scratch = (Cand*)(ws + workspace_bytes(G, R.n) - exact_scratch_bytes(G));
         hipLaunchKernelGGL((exact_kernel<MODE, double, F, INV, true>), dim3(kExactSerialBlocks),
-                           dim3(64), 0, st, G, R, o, scratch);
+                           dim3(64), 0, st, G, R, o, ws.scratch);
     }
     return check_launch("exact_kernel (reference mode)");
+}
+
+// A reference-mode entry's way in, as run_trace: resolve, the flags, the entry's own refusal, the
+// launch for the flags' precision (float32 solves or float64) and masking (invalid=True or not).
+template <int MODE>
+static int run_reference(const sphrt_plan* plan, const sphrt_rays* rays, int flags,
+                         const char* refusal, const TraceOut<double>& o, void* workspace,
+                         size_t workspace_size, void* stream) {
+    GridDev G;
+    RaysDev R;
+    if (int e = resolve(plan, rays, G, R, stream)) return e;
+    DeviceGuard guard(plan->device);
+    if (flags & ~(SPHRT_TRACE_F32 | SPHRT_TRACE_INVALID | SPHRT_TRACE_FRESH_RAYS))
+        return fail("unknown trace flags %d", flags);
+    if (refusal) return fail("%s", refusal);
+    R.fresh = (flags & SPHRT_TRACE_FRESH_RAYS) != 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (MODE == MODE_EMIT && hipMemsetAsync(o.n_over, 0, sizeof(int64_t), st) != hipSuccess)
+        return fail("memset failed");
+    const bool f32 = (flags & SPHRT_TRACE_F32) != 0, inv = (flags & SPHRT_TRACE_INVALID) != 0;
+    if (f32)
+        return inv ? launch_reference<MODE, float, true>(G, R, o, workspace, workspace_size, st)
+                   : launch_reference<MODE, float, false>(G, R, o, workspace, workspace_size, st);
+    return inv ? launch_reference<MODE, double, true>(G, R, o, workspace, workspace_size, st)
+               : launch_reference<MODE, double, false>(G, R, o, workspace, workspace_size, st);
 }
 
 extern "C" int sphrt_trace_reference_emit(const sphrt_plan* plan, const sphrt_rays* rays,
                                           int flags, const int64_t* bound_ptr, int32_t* counts,
                                           int32_t* svox, double* slen, int64_t* n_over,
                                           void* workspace, size_t workspace_size, void* stream) {
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    if (flags & ~(SPHRT_TRACE_F32 | SPHRT_TRACE_INVALID | SPHRT_TRACE_FRESH_RAYS))
-        return fail("unknown trace flags %d", flags);
-    if (!bound_ptr || !counts || !svox || !slen || !n_over) return fail("null emit argument");
-    R.fresh = (flags & SPHRT_TRACE_FRESH_RAYS) != 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(n_over, 0, sizeof(int64_t), st) != hipSuccess) return fail("memset failed");
-    TraceOut<double> o{};
-    o.row_ptr = bound_ptr;
-    o.counts = counts;
-    o.vox = svox;
-    o.len = slen;
-    o.n_over = (unsigned long long*)n_over;
-    const bool f32 = (flags & SPHRT_TRACE_F32) != 0, inv = (flags & SPHRT_TRACE_INVALID) != 0;
-    if (f32)
-        return inv ? launch_reference<MODE_EMIT, float, true>(G, R, o, workspace, workspace_size, st)
-                   : launch_reference<MODE_EMIT, float, false>(G, R, o, workspace, workspace_size, st);
-    return inv ? launch_reference<MODE_EMIT, double, true>(G, R, o, workspace, workspace_size, st)
-               : launch_reference<MODE_EMIT, double, false>(G, R, o, workspace, workspace_size, st);
+    const bool null_arg = !bound_ptr || !counts || !svox || !slen || !n_over;
+    return run_reference<MODE_EMIT>(plan, rays, flags, null_arg ? "null emit argument" : nullptr,
+                                    csr_out(counts, bound_ptr, svox, slen, n_over), workspace,
+                                    workspace_size, stream);
 }
 
+// Two passes: the counts (row_ptr null), then the rows at their scanned row_ptr.
 extern "C" int sphrt_trace_reference(const sphrt_plan* plan, const sphrt_rays* rays, int flags,
                                      int32_t* counts, const int64_t* row_ptr, int32_t* vox,
                                      double* len, void* workspace, size_t workspace_size,
                                      void* stream) {
-    GridDev G;
-    RaysDev R;
-    if (int e = resolve(plan, rays, G, R, stream)) return e;
-    DeviceGuard guard(plan->device);
-    if (flags & ~(SPHRT_TRACE_F32 | SPHRT_TRACE_INVALID | SPHRT_TRACE_FRESH_RAYS))
-        return fail("unknown trace flags %d", flags);
-    R.fresh = (flags & SPHRT_TRACE_FRESH_RAYS) != 0;
-    hipStream_t st = (hipStream_t)stream;
-    TraceOut<double> o{};
-    const bool f32 = (flags & SPHRT_TRACE_F32) != 0, inv = (flags & SPHRT_TRACE_INVALID) != 0;
-    if (!row_ptr) {
-        if (!counts) return fail("null counts");
-        o.counts = counts;
-        if (f32)
-            return inv ? launch_reference<MODE_COUNT, float, true>(G, R, o, workspace, workspace_size, st)
-                       : launch_reference<MODE_COUNT, float, false>(G, R, o, workspace, workspace_size, st);
-        return inv ? launch_reference<MODE_COUNT, double, true>(G, R, o, workspace, workspace_size, st)
-                   : launch_reference<MODE_COUNT, double, false>(G, R, o, workspace, workspace_size, st);
-    }
-    if (!vox || !len) return fail("null fill output");
-    o.row_ptr = row_ptr;
-    o.vox = vox;
-    o.len = len;
-    if (f32)
-        return inv ? launch_reference<MODE_FILL, float, true>(G, R, o, workspace, workspace_size, st)
-                   : launch_reference<MODE_FILL, float, false>(G, R, o, workspace, workspace_size, st);
-    return inv ? launch_reference<MODE_FILL, double, true>(G, R, o, workspace, workspace_size, st)
-               : launch_reference<MODE_FILL, double, false>(G, R, o, workspace, workspace_size, st);
+    if (!row_ptr)
+        return run_reference<MODE_COUNT>(plan, rays, flags, counts ? nullptr : "null counts",
+                                         csr_out(counts, nullptr, nullptr, nullptr), workspace,
+                                         workspace_size, stream);
+    return run_reference<MODE_FILL>(plan, rays, flags, vox && len ? nullptr : "null fill output",
+                                    csr_out(nullptr, row_ptr, vox, len), workspace,
+                                    workspace_size, stream);
 }
