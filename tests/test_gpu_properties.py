@@ -12,7 +12,7 @@ import pytest
 import torch as tr
 
 import golden_cases as gc
-from gpu_helpers import exact_stats as _exact_stats
+from gpu_helpers import _check_granule_tables, _stage_col, exact_stats as _exact_stats
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pytestmark = pytest.mark.gpu
@@ -170,15 +170,6 @@ def test_granule_tables_partial_last_granule(gpu):
     _check_granule_tables(grid, geom, op, gpu, tab_bytes=2)
 
 
-def _stage_col(v, shape, brick):
-    """Natural voxel -> brick-staged column (apply.hip stage_col), numpy."""
-    (nr, ne, na), (br, be, ba) = shape, brick
-    r, e, a = v // (ne * na), (v // na) % ne, v % na
-    nbe, nba = -(-ne // be), -(-na // ba)
-    blk = ((r // br) * nbe + e // be) * nba + a // ba
-    return blk * (br * be * ba) + ((r % br) * be + e % be) * ba + a % ba
-
-
 def test_brick_staged_tables(gpu, monkeypatch):
     """Brick staging forced on a grid no brick divides (padded staging, 3 channels growing the
     stage): tables and loc address the staged columns, and the staged table forward equals the
@@ -208,53 +199,6 @@ def test_brick_staged_tables(gpu, monkeypatch):
         off.copy_(x32)
         assert off.data_ptr() % 16 != 0
         assert tr.equal(op(off), op(x32))
-
-
-def _check_granule_tables(grid, geom, op, gpu, tab_bytes):
-    from sph_raytracer_amd import _lib
-    csr = op._csr
-    blocks = csr['blocks'].cpu().numpy().reshape(-1, _lib.BLOCK_FIELDS)
-    vox = csr['vox'].cpu().numpy().view(np.uint32)[:csr['total']]
-    loc = csr['loc'].cpu().numpy().view(np.uint16)[:csr['total']]
-    tab = csr['tab'].cpu().numpy()
-    assert csr['desc'].tab_bytes == tab_bytes
-    tab = tab.view(np.uint16).astype(np.int64) if tab_bytes == 2 else tab.astype(np.int64)
-    s0, s1, n_tab = blocks[:, 2], blocks[:, 3], blocks[:, 5]
-    assert (n_tab >= 0).all() and (n_tab <= s1 - s0).all() and csr['desc'].n_fallback == 0
-    owner = np.repeat(np.arange(len(blocks)), s1 - s0)
-    off = (loc & 0x7fff).astype(np.int64)   # byte offset in the float LDS image (zero granule first)
-    assert (off % 4 == 0).all() and (off >= 16).all()
-    slot = off // 4 - 4
-    assert (slot // 4 < n_tab[owner]).all()
-    v = (vox & 0x7fffffff).astype(np.int64)
-    d = csr['desc']
-    if d.stage_shape[0] > 0:                 # brick staging: tables address the staged columns
-        v = _stage_col(v, tuple(d.stage_shape), tuple(d.stage_brick))
-    stride = csr['desc'].tab_stride
-    assert stride >= n_tab.max() and stride % 64 == 0
-    assert np.array_equal(tab[owner * stride + slot // 4], v >> 2)
-    assert np.array_equal(slot % 4, v % 4)
-    assert np.array_equal(loc >> 15, vox >> 31)
-    for b in range(0, len(blocks), 97):
-        t0 = b * stride
-        assert (np.diff(tab[t0:t0 + n_tab[b]]) > 0).all()
-    g = tr.Generator(device=gpu).manual_seed(3)
-    for dt in (tr.float32, tr.float64):
-        x = tr.rand(grid.shape, dtype=dt, device=gpu, generator=g)
-        y = tr.rand(geom.shape, dtype=dt, device=gpu, generator=g)
-        xc = tr.rand((2,) + tuple(grid.shape), dtype=dt, device=gpu, generator=g)
-        a, at, ac = op(x), op.T(y), op(xc)
-        descs = [csr['desc'], op._transposed()['desc']]
-        saved = [(d.loc, d.tab) for d in descs]
-        try:
-            for d in descs:
-                d.loc, d.tab = None, None
-            assert tr.equal(op(x), a)
-            assert tr.equal(op.T(y), at)
-            assert tr.equal(op(xc), ac)
-        finally:
-            for d, (lc, tb) in zip(descs, saved):
-                d.loc, d.tab = lc, tb
 
 
 @pytest.mark.parametrize('runs', ['auto', 'on'])
@@ -973,29 +917,10 @@ def test_onepass_tables_equal_twopass(grid_shape, staged, gpu, monkeypatch):
 def _expected_runs(csr, n_blocks_fields):
     """Host restatement of block_runs_kernel: per block, the runs of consecutive rays of its rows
     and of its share of the empty list (None for more than MAX_RUNS)."""
-    from sph_raytracer_amd import _lib
+    import csr_cases
     blocks = csr['blocks'].cpu().numpy().reshape(-1, n_blocks_fields)
-    row_ray = csr['row_ray'].cpu().numpy()
-    empty = csr['empty_ray'].cpu().numpy()
-    n_rows = csr['n'] - blocks[-1, 1]
-
-    def runs(v):
-        if len(v) == 0:
-            return []
-        cut = np.nonzero(np.diff(v) != 1)[0] + 1
-        starts = np.concatenate(([0], cut))
-        ends = np.concatenate((cut, [len(v)]))
-        return [(int(a), int(v[a]), int(b - a)) for a, b in zip(starts, ends)]
-
-    out = []
-    for b in range(len(blocks)):
-        k0 = blocks[b, 4]
-        k1 = blocks[b + 1, 4] if b + 1 < len(blocks) else n_rows
-        rr = runs(row_ray[k0:k1])
-        er = runs(empty[blocks[b, 0]:blocks[b, 1]])
-        out.append((rr if len(rr) <= _lib.MAX_RUNS else None,
-                    er if len(er) <= _lib.MAX_RUNS else None))
-    return out
+    return csr_cases.expected_runs(blocks, csr['row_ray'].cpu().numpy(),
+                                   csr['empty_ray'].cpu().numpy(), csr['n'])
 
 
 def test_run_records(c2, gpu, monkeypatch):
