@@ -177,6 +177,40 @@ int sphrt_trace_compact(int64_t n, const int64_t *bound_ptr, const int32_t *svox
                         const double *slen, const int64_t *row_ptr, int32_t *vox, double *len,
                         void *stream);
 
+/* TEST HOOK (tests/test_gpu_exact_sort.py): the sorts of the exact path — the device emulation of
+ * the reference's unstable torch.sort — on lists handed in from the host, one workgroup per list.
+ * t: n_lists x K distances in the trace's concatenation order; reg: the region every entry writes
+ * (the device forms pay = index << 16 | (reg + 2) as the trace does; reg in [-2, 65533]); start:
+ * three int32 per list, the start voxel; nbr / nbe: boundary counts, entries below 2 nbr are
+ * sphere crossings, below 2 nbr + 2 nbe cone crossings, then half-planes, entry K - 1 the start
+ * entry.  method:
+ *   SPHRT_SORT_SERIAL_AOS  the serial emulation on one lane over a global-memory list (grids whose
+ *                          list does not fit LDS); workspace: sphrt_exact_sort_workspace_bytes
+ *   SPHRT_SORT_SERIAL_SOA  the same on one lane over the LDS list (the wave kernel's NaN fallback)
+ *   SPHRT_SORT_WAVE1 / 4   the wave-parallel emulation with one wave / four waves per list;
+ *                          `invalid` selects the invalid=True instantiation (ties of infinite
+ *                          distances matter)
+ *   SPHRT_SORT_NETWORK     the reference mode's register sort alone; a list it refuses writes only
+ *                          its flag, nothing falls back
+ * Writes the sorted distances (t_out) and payloads (pay_out), n_lists x K each, and per list
+ * SPHRT_SORT_INFO_FIELDS int64 `info`: depth-limit ranges rank-sorted, heap-sorted (wave methods),
+ * the network's accepted flag, 1 when a wave method met a NaN (it then sorts nothing).  Lists must
+ * hold no NaN, except for SPHRT_SORT_NETWORK: the serial emulation's unguarded scans are
+ * undefined over NaN, as std::sort's are.  A K outside [1, sphrt_exact_sort_max_k(method)] is an
+ * error (the network: [2, 512]; -1 for an unknown method). */
+#define SPHRT_SORT_SERIAL_AOS 0
+#define SPHRT_SORT_SERIAL_SOA 1
+#define SPHRT_SORT_WAVE1 2
+#define SPHRT_SORT_WAVE4 3
+#define SPHRT_SORT_NETWORK 4
+#define SPHRT_SORT_INFO_FIELDS 4
+int64_t sphrt_exact_sort_max_k(int method);
+size_t sphrt_exact_sort_workspace_bytes(int method, int64_t n_lists, int64_t K);
+int sphrt_exact_sort_lists(const double *t, const int32_t *reg, const int32_t *start,
+                           int64_t n_lists, int64_t K, int32_t nbr, int32_t nbe, int method,
+                           int invalid, double *t_out, uint32_t *pay_out, int64_t *info,
+                           void *workspace, size_t workspace_size, void *stream);
+
 /* ---- on-device cone-beam ray directions (replaces ConeRectGeom.rays, geometry.py:493-508, and
  * ConeCircGeom.rays, geometry.py:570-582) ----------------------------------------------------- */
 /* rays[v][a][b][0..2] for n_views views of h x w pixels, bit-identical to the torch expressions.

@@ -69,6 +69,8 @@ def load():
         lib.ora_set_sqrt.argtypes = [P]
         lib.ora_set_sqrt_f32.argtypes = [P]
         lib.ora_introsort.argtypes = [P, P, I]
+        lib.ora_introsort_ranges.argtypes = [P, P, I, P, I]
+        lib.ora_introsort_ranges.restype = I
         for sfx in ('', '_f32'):
             getattr(lib, 'ora_solve' + sfx).argtypes = [ctypes.POINTER(Grid), I, P, P, N, P, P, P]
             getattr(lib, 'ora_trace_dense' + sfx).argtypes = [ctypes.POINTER(Grid), P, P, P, N, I,
@@ -121,6 +123,18 @@ def introsort(values):
     idx = np.zeros(len(t), np.int32)
     load().ora_introsort(t.ctypes.data, idx.ctypes.data, len(t))
     return t, idx
+
+
+def introsort_ranges(values):
+    """introsort(values), and the ranges the depth limit (2 floor(log2 n)) sent to the heapsort:
+    (sorted values, permutation, (m, 2) int32 of [first, last) positions in the sorted output)."""
+    t = _c(values, np.float64).copy()
+    idx = np.zeros(len(t), np.int32)
+    cap = max(len(t) // 16, 1)          # the ranges are disjoint and longer than 16
+    ranges = np.zeros((cap, 2), np.int32)
+    m = load().ora_introsort_ranges(t.ctypes.data, idx.ctypes.data, len(t), ranges.ctypes.data, cap)
+    assert m <= cap
+    return t, idx, ranges[:m].copy()
 
 
 def solve(grid, family, xs, rays):

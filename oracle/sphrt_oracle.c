@@ -140,17 +140,31 @@ static void heapsort_range(ora_item *v, int first, int last) {
     }
 }
 
-static void intro_loop(ora_item *v, int first, int last, int depth) {
+/* The ranges the depth limit heap-sorts, for ora_introsort_ranges: (first, last) pairs, the
+ * first `cap` of them stored, all of them counted. */
+typedef struct {
+    int *pairs;
+    int cap, n;
+} ora_ranges;
+
+static void intro_loop(ora_item *v, int first, int last, int depth, ora_ranges *hr) {
     while (last - first > 16) {
         int cut;
         if (depth == 0) {
+            if (hr) {
+                if (hr->n < hr->cap) {
+                    hr->pairs[2 * hr->n] = first;
+                    hr->pairs[2 * hr->n + 1] = last;
+                }
+                hr->n++;
+            }
             heapsort_range(v, first, last);
             return;
         }
         --depth;
         median_first(v, first, first + 1, first + (last - first) / 2, last - 1);
         cut = hoare(v, first + 1, last, first);
-        intro_loop(v, cut, last, depth);
+        intro_loop(v, cut, last, depth, hr);
         last = cut;
     }
 }
@@ -165,14 +179,14 @@ static void lin_insert(ora_item *v, int last) {
     v[last] = val;
 }
 
-void ora_introsort(double *t, int *idx, int n) {
+static void introsort_run(double *t, int *idx, int n, ora_ranges *hr) {
     ora_item *v = (ora_item *)malloc(sizeof(ora_item) * (n > 0 ? n : 1));
     int i, lg = 0;
     for (i = 0; i < n; ++i) { v[i].t = t[i]; v[i].idx = i; }
     while ((2 << lg) <= n) ++lg;     /* floor(log2(n)) */
     if (n > 1) {
         int lim = n > 16 ? 16 : n;
-        intro_loop(v, 0, n, 2 * lg);
+        intro_loop(v, 0, n, 2 * lg, hr);
         for (i = 1; i < lim; ++i) {
             if (lt(&v[i], &v[0])) {
                 ora_item val = v[i];
@@ -186,6 +200,20 @@ void ora_introsort(double *t, int *idx, int n) {
     }
     for (i = 0; i < n; ++i) { t[i] = v[i].t; idx[i] = v[i].idx; }
     free(v);
+}
+
+void ora_introsort(double *t, int *idx, int n) { introsort_run(t, idx, n, NULL); }
+
+/* The same sort, reporting the ranges [first, last) of the list that the depth limit sent to the
+ * heapsort (positions in the sorted output: nothing crosses a range's ends afterwards).  Returns
+ * their number; `ranges` takes the first `cap` as (first, last) pairs. */
+int ora_introsort_ranges(double *t, int *idx, int n, int *ranges, int cap) {
+    ora_ranges hr;
+    hr.pairs = ranges;
+    hr.cap = ranges ? cap : 0;
+    hr.n = 0;
+    introsort_run(t, idx, n, &hr);
+    return hr.n;
 }
 
 int64_t ora_candidates(const ora_grid *g) {

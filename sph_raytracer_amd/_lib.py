@@ -152,8 +152,16 @@ _SIGNATURES = [
     ('sphrt_fixed_exponent_host', c_int, [c_dbl, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     ('sphrt_fixed_quantise_host', None, [c_dbl, c_i32, ctypes.POINTER(c_i64)]),
     ('sphrt_fixed_value_host', c_dbl, [c_i64, c_i64, c_i32, c_i32]),
+    # test hook: the exact path's sorts on host lists (tests/test_gpu_exact_sort.py)
+    ('sphrt_exact_sort_max_k', c_i64, [c_int]),
+    ('sphrt_exact_sort_workspace_bytes', ctypes.c_size_t, [c_int, c_i64, c_i64]),
+    ('sphrt_exact_sort_lists', c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_int, c_int,
+                                       c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
 ]
 EXPORTED = [s[0] for s in _SIGNATURES]
+# sphrt_exact_sort_lists methods and info fields (sphrt.h)
+SORT_SERIAL_AOS, SORT_SERIAL_SOA, SORT_WAVE1, SORT_WAVE4, SORT_NETWORK = range(5)
+SORT_INFO_FIELDS = 4
 TRACE_F32, TRACE_INVALID, TRACE_FRESH_RAYS = 1, 2, 4   # sphrt_trace_reference flags (sphrt.h)
 
 _lib = None

@@ -20,7 +20,8 @@ OUT = os.path.join(HERE, 'lib', 'libsphrt.so')
 FAST_OUT = os.path.join(HERE, 'lib', '_sphrt_fast.so')   # CPython entry for steady-state calls
 SOURCES = ['api.hip', 'trace.hip', 'apply.hip', 'transpose.hip', 'rays.hip', 'loss.hip',
            'fixed.hip']
-HEADERS = ['common.hpp', 'solve.hpp', 'introsort.hpp', 'stage.hpp', 'fixed.hpp']
+HEADERS = ['common.hpp', 'solve.hpp', 'introsort.hpp', 'stage.hpp', 'fixed.hpp',
+           'exact_sort_phase.inc']
 ARCH = os.environ.get('SPHRT_ARCH', 'gfx950')
 
 

@@ -2,9 +2,11 @@
 //
 // trace_indices sorts every ray's candidate distances with torch.sort (raytracer.py:131), which on
 // CPU is libstdc++ std::sort over (value, index) pairs compared by value with operator< (verified
-// here against torch on random tie-heavy rows: tests/test_introsort_emulation.py).  When two
-// crossings that update the same region row sit at exactly the same distance, their order — and
-// with it the voxel of the following segments — is whatever that introsort produces.  This header
+// by the CPU oracle's port against torch on tie-heavy rows and on lists that reach the depth limit:
+// tests/test_oracle.py, tests/test_sort_cases_cpu.py; this header against that oracle on the
+// device: tests/test_gpu_exact_sort.py).  When two crossings that update the same region row sit
+// at exactly the same distance, their order — and with it the voxel of the following segments —
+// is whatever that introsort produces.  This header
 // reproduces it step for step (median-of-three pivot, unguarded Hoare partition, depth limit
 // 2*floor(log2 n) with heapsort fallback, threshold 16, final insertion sort) on one lane.
 #pragma once

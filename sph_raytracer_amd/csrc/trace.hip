@@ -1774,8 +1774,11 @@ __device__ __forceinline__ void exact_heap_range(const SoaList& v, double* tk, u
         }
         lpos[p] = r;
     }
-    if (lane == 0 && n_heap) atomicAdd(n_heap + (__ballot(amb) != 0 ? 1 : 0), 1ull);
-    if (__ballot(amb) != 0) {
+    // (the vote before lane 0 is alone: inside its branch a ballot sees lane 0's pairs only, and
+    // a range another lane found ambiguous was counted as rank-sorted)
+    const bool heap = __ballot(amb) != 0;
+    if (lane == 0 && n_heap) atomicAdd(n_heap + (heap ? 1 : 0), 1ull);
+    if (heap) {
         wave_sync();
         if (lane == 0) heap_sort(v, first, last);
         wave_sync();
@@ -1870,6 +1873,7 @@ __device__ bool network_sort(const GridDev& G, const double* tk, const uint32_t*
     }
     return __ballot(amb) == 0;
 }
+constexpr int kNetworkMaxK = 512;   // the widest network: 8 keys per lane
 template <bool INV>
 __device__ __forceinline__ bool reference_network(const GridDev& G, const double* tk,
                                                   const uint32_t* pk, double* ts, uint32_t* ps,
@@ -1881,9 +1885,63 @@ __device__ __forceinline__ bool reference_network(const GridDev& G, const double
         if (K <= 64) return network_sort<1>(G, tk, pk, ts, ps, K, lane, s);
         if (K <= 128) return network_sort<2>(G, tk, pk, ts, ps, K, lane, s);
         if (K <= 256) return network_sort<4>(G, tk, pk, ts, ps, K, lane, s);
-        if (K <= 512) return network_sort<8>(G, tk, pk, ts, ps, K, lane, s);
+        if (K <= kNetworkMaxK)
+            return network_sort<kNetworkMaxK / 64>(G, tk, pk, ts, ps, K, lane, s);
         return false;
     }
+}
+
+// The sort phase (exact_sort_phase.inc) as a function, for the test hook's kernel below;
+// exact_wave_kernel includes the same text in place.  ExactLds is that kernel's LDS layout
+// (exact_wave_lds(K, W) bytes: the arrays of K entries, per wave the partition stack, the W
+// top-level ranges) and exact_sort_init what it sets up before the sort: every entry a leaf of its
+// own, the whole list as the one top-level range with the reference's depth limit.
+struct ExactLds {
+    double *tk, *ts;                      // list (distance) in current order, sorted list
+    uint32_t *pk, *ps;                    // their payloads
+    int32_t *lpos, *rpos;                 // left / right stops by rank
+    uint32_t* leaf;                       // leaf range lo | hi << 16
+    int *st_first, *st_last, *st_depth;   // this wave's stack
+    int* top;                             // (first, last, depth) of the W top-level ranges
+};
+__device__ __forceinline__ ExactLds exact_lds_carve(unsigned char* lds, int K, int W, int wid) {
+    ExactLds L;
+    L.tk = reinterpret_cast<double*>(lds);
+    L.ts = L.tk + K;
+    L.pk = reinterpret_cast<uint32_t*>(L.ts + K);
+    L.ps = L.pk + K;
+    L.lpos = reinterpret_cast<int32_t*>(L.ps + K);
+    L.rpos = L.lpos + K;
+    L.leaf = reinterpret_cast<uint32_t*>(L.rpos + K);
+    L.st_first = reinterpret_cast<int*>(L.leaf + K) + wid * 3 * kExactStack;
+    L.st_last = L.st_first + kExactStack;
+    L.st_depth = L.st_last + kExactStack;
+    L.top = reinterpret_cast<int*>(L.leaf + K) + W * 3 * kExactStack;
+    return L;
+}
+template <int W>
+__device__ __forceinline__ void exact_sort_init(const ExactLds& L, int K, int tid) {
+    for (int p = tid; p < K; p += 64 * W) L.leaf[p] = (uint32_t)p | ((uint32_t)(p + 1) << 16);
+    if (tid == 0) {
+        L.top[0] = 0;
+        L.top[1] = K;
+        L.top[2] = 2 * (31 - __builtin_clz((unsigned)max(K, 1)));
+    }
+}
+// s: the list's start voxel (entries_conflict); n_heap: the two heap-range counters, or null.
+template <bool INV, int W>
+__device__ __forceinline__ void exact_wave_sort(const ExactLds& L, int K, int r_lim, int e_lim,
+                                                const int* s, int tid,
+                                                unsigned long long* n_heap) {
+    double *const tk = L.tk, *const ts = L.ts;
+    uint32_t *const pk = L.pk, *const ps = L.ps, *const leaf = L.leaf;
+    int32_t *const lpos = L.lpos, *const rpos = L.rpos;
+    int *const st_first = L.st_first, *const st_last = L.st_last, *const st_depth = L.st_depth;
+    int* const top = L.top;
+    const SoaList v{tk, pk};
+    const int lane = tid & 63, wid = tid >> 6;
+    const uint64_t below = lanemask_lt(lane);
+#include "exact_sort_phase.inc"
 }
 
 // W waves per ray.  The candidates and the leaf ranks are spread over all 64 W lanes; the
@@ -1949,77 +2007,8 @@ __global__ __launch_bounds__(64 * W) void exact_wave_kernel(GridDev G, RaysDev R
             __syncthreads();
             return;
         }
-        // ---- partition phase (uniform control flow per wave) ----
-        // the top levels, breadth-first: range w of level l splits into ranges w and w + 2^l
-#pragma unroll
-        for (int n = 1; n < W; n *= 2) {
-            if (wid < n) {
-                const int f = top[3 * wid], l = top[3 * wid + 1], dep = top[3 * wid + 2];
-                int cut = l, nd = dep;
-                if (l - f > kIntroThreshold && dep > 0) {
-                    cut = exact_partition(v, tk, pk, lpos, rpos, f, l, lane, below);
-                    nd = dep - 1;
-                }
-                if (lane == 0) {
-                    top[3 * wid + 1] = cut;
-                    top[3 * wid + 2] = nd;
-                    top[3 * (wid + n)] = cut;
-                    top[3 * (wid + n) + 1] = l;
-                    top[3 * (wid + n) + 2] = nd;
-                }
-            }
-            __syncthreads();
-        }
-        // then each wave its range, depth first
-        int sp = 0;
-        int first = top[3 * wid], last = top[3 * wid + 1], depth = top[3 * wid + 2];
-        bool have = last - first > 1;
-        while (have) {
-            while (last - first > kIntroThreshold) {
-                if (depth == 0) {                      // the reference's heapsort
-                    exact_heap_range<INV>(v, tk, pk, ts, ps, lpos, first, last, K, r_lim, e_lim,
-                                          s, lane, o.n_heap);
-                    first = last;                      // sorted: no leaf
-                    break;
-                }
-                --depth;
-                const int cut = exact_partition(v, tk, pk, lpos, rpos, first, last, lane, below);
-                if (lane == 0) {
-                    st_first[sp] = cut;
-                    st_last[sp] = last;
-                    st_depth[sp] = depth;
-                }
-                ++sp;
-                last = cut;
-                wave_sync();
-            }
-            if (last - first > 1) {                    // a leaf: its range, for the final ranks
-                const uint32_t code = (uint32_t)first | ((uint32_t)last << 16);
-                for (int p = first + lane; p < last; p += 64) leaf[p] = code;
-            }
-            have = sp > 0;
-            if (have) {
-                --sp;
-                first = st_first[sp];
-                last = st_last[sp];
-                depth = st_depth[sp];
-            }
-        }
-        __syncthreads();
-        // ---- final insertion sort = stable sort inside each leaf, as ranks ----
-        for (int p = tid; p < K; p += 64 * W) {
-            const uint32_t code = leaf[p];
-            const int lo = (int)(code & 0xffffu), hi = (int)(code >> 16);
-            const double t = tk[p];
-            int r = lo;
-            for (int j = lo; j < hi; ++j) {
-                const double u = tk[j];
-                r += (u < t || (u == t && j < p)) ? 1 : 0;
-            }
-            ts[r] = t;
-            ps[r] = pk[p];
-        }
-        __syncthreads();
+        unsigned long long* const& n_heap = o.n_heap;
+#include "exact_sort_phase.inc"
         // (the pre-sort list and the left-stop list are free now: compacted segments go there)
         if (wid == 0) exact_walk_wave<MODE, T, F, INV>(G, o, ray, s, ts, ps, lpos, tk, lane);
         __syncthreads();
@@ -2653,4 +2642,183 @@ extern "C" int sphrt_trace_reference(const sphrt_plan* plan, const sphrt_rays* r
     return run_reference<MODE_FILL>(plan, rays, flags, vox && len ? nullptr : "null fill output",
                                     csr_out(nullptr, row_ptr, vox, len), workspace,
                                     workspace_size, stream);
+}
+
+// ---- test hook: the exact path's sorts on lists handed in from the host -----------------------
+// One workgroup per list.  The list is laid out as the trace lays out a ray's: entry c carries
+// pay = c << 16 | (reg + 2), entry K - 1 is the start entry, entries below 2 nbr / 2 nbr + 2 nbe
+// are sphere / cone crossings.  info (SPHRT_SORT_INFO_FIELDS per list, zeroed by the entry):
+// depth-limit ranges rank-sorted, heap-sorted; the network's accepted flag; a NaN met by a wave
+// method (which then sorts nothing: the trace sends such a list to the serial sort).
+namespace sphrt {
+
+__device__ __forceinline__ uint32_t sort_list_pay(int c, int reg) {
+    return ((uint32_t)c << 16) | (uint32_t)(reg + 2);
+}
+
+// exact_kernel's sort: introsort(CandList) on lane 0, the list in global memory.
+__global__ __launch_bounds__(64) void sort_lists_aos_kernel(const double* __restrict__ t,
+                                                            const int32_t* __restrict__ reg, int K,
+                                                            Cand* scratch, double* t_out,
+                                                            uint32_t* pay_out) {
+    const int lane = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * K;
+    const CandList v{scratch + base};
+    for (int c = lane; c < K; c += 64)
+        v.set(c, Cand{t[base + c], sort_list_pay(c, reg[base + c]), 0u});
+    __syncthreads();
+    if (lane == 0) introsort(v, K);
+    __syncthreads();
+    for (int c = lane; c < K; c += 64) {
+        const Cand e = v.get(c);
+        t_out[base + c] = e.t;
+        pay_out[base + c] = e.pay;
+    }
+}
+
+// The sorts over exact_wave_kernel's LDS list (exact_wave_lds(K, W) bytes): introsort(SoaList) on
+// one lane, exact_wave_sort, reference_network<false> alone.
+template <int METHOD, bool INV, int W>
+__global__ __launch_bounds__(64 * W) void sort_lists_lds_kernel(GridDev G,
+                                                                const double* __restrict__ t,
+                                                                const int32_t* __restrict__ reg,
+                                                                const int32_t* __restrict__ start,
+                                                                double* t_out, uint32_t* pay_out,
+                                                                int64_t* info) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sl_lds[];
+    const int K = G.K;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const ExactLds L = exact_lds_carve(sl_lds, K, W, wid);
+    const int64_t base = (int64_t)blockIdx.x * K;
+    int64_t* my = info + (int64_t)blockIdx.x * SPHRT_SORT_INFO_FIELDS;
+    const int s[3] = {start[3 * blockIdx.x], start[3 * blockIdx.x + 1], start[3 * blockIdx.x + 2]};
+    for (int c = tid; c < K; c += 64 * W) {
+        L.tk[c] = t[base + c];
+        L.pk[c] = sort_list_pay(c, reg[base + c]);
+    }
+    exact_sort_init<W>(L, K, tid);
+    __syncthreads();
+    const double* st = L.ts;
+    const uint32_t* sp = L.ps;
+    if constexpr (METHOD == SPHRT_SORT_NETWORK) {
+        const bool ok = reference_network<false>(G, L.tk, L.pk, L.ts, L.ps, lane, s);
+        if (tid == 0) my[2] = ok ? 1 : 0;
+        if (!ok) return;                               // (uniform: the network ends in a ballot)
+        __syncthreads();
+    } else if constexpr (METHOD == SPHRT_SORT_SERIAL_SOA) {
+        if (tid == 0) introsort(SoaList{L.tk, L.pk}, K);
+        __syncthreads();
+        st = L.tk;
+        sp = L.pk;
+    } else {
+        int nan = 0;
+        for (int p = tid; p < K; p += 64 * W) nan |= __builtin_isnan(L.tk[p]) ? 1 : 0;
+        if (__syncthreads_or(nan)) {
+            if (tid == 0) my[3] = 1;
+            return;
+        }
+        const int r_lim = 2 * G.nbr, e_lim = 2 * G.nbr + 2 * G.nbe;
+        exact_wave_sort<INV, W>(L, K, r_lim, e_lim, s, tid,
+                                reinterpret_cast<unsigned long long*>(my));
+    }
+    for (int c = tid; c < K; c += 64 * W) {
+        t_out[base + c] = st[c];
+        pay_out[base + c] = sp[c];
+    }
+}
+
+// The largest list a method holds: a candidate index and the list's length in 16 bits of the
+// payload / the leaf codes (the serial sort over global memory), the LDS list of one workgroup
+// of W waves, the widest network.
+static int64_t sort_max_k(int method) {
+    auto lds_max = [](int W) {
+        return (int64_t)((kExactWaveLdsMax - exact_wave_lds(0, W)) / kExactWaveEntryBytes);
+    };
+    switch (method) {
+    case SPHRT_SORT_SERIAL_AOS: return 1 << 16;
+    case SPHRT_SORT_SERIAL_SOA:
+    case SPHRT_SORT_WAVE1: return lds_max(1);
+    case SPHRT_SORT_WAVE4: return lds_max(kExactWaves);
+    case SPHRT_SORT_NETWORK: return kNetworkMaxK;
+    default: return -1;
+    }
+}
+constexpr int64_t kSortMaxLists = 1 << 20;
+
+template <int METHOD, bool INV, int W>
+static void launch_sort_lds(const GridDev& G, int64_t n_lists, const double* t, const int32_t* reg,
+                            const int32_t* start, double* t_out, uint32_t* pay_out, int64_t* info,
+                            hipStream_t st) {
+    hipLaunchKernelGGL((sort_lists_lds_kernel<METHOD, INV, W>), dim3((unsigned)n_lists),
+                       dim3(64 * W), exact_wave_lds(G.K, W), st, G, t, reg, start, t_out, pay_out,
+                       info);
+}
+
+}  // namespace sphrt
+
+extern "C" int64_t sphrt_exact_sort_max_k(int method) { return sort_max_k(method); }
+
+extern "C" size_t sphrt_exact_sort_workspace_bytes(int method, int64_t n_lists, int64_t K) {
+    if (method != SPHRT_SORT_SERIAL_AOS || n_lists <= 0 || K <= 0) return 0;
+    return (size_t)n_lists * (size_t)K * sizeof(Cand);
+}
+
+extern "C" int sphrt_exact_sort_lists(const double* t, const int32_t* reg, const int32_t* start,
+                                      int64_t n_lists, int64_t K, int32_t nbr, int32_t nbe,
+                                      int method, int invalid, double* t_out, uint32_t* pay_out,
+                                      int64_t* info, void* workspace, size_t workspace_size,
+                                      void* stream) {
+    const int64_t max_k = sort_max_k(method);
+    if (max_k < 0) return fail("unknown sort method %d", method);
+    if (n_lists < 0 || n_lists > kSortMaxLists)
+        return fail("list count %lld out of range", (long long)n_lists);
+    // (the network's composite key needs an index bit: a traced list has K >= 11)
+    const int64_t min_k = method == SPHRT_SORT_NETWORK ? 2 : 1;
+    if (K < min_k || K > max_k)
+        return fail("sort method %d holds lists of %lld to %lld entries, not %lld", method,
+                    (long long)min_k, (long long)max_k, (long long)K);
+    if (nbr < 0 || nbe < 0 || nbr > (1 << 16) || nbe > (1 << 16))
+        return fail("boundary counts out of range");
+    if (n_lists == 0) return 0;
+    if (!t || !reg || !start || !t_out || !pay_out || !info) return fail("null sort argument");
+    const size_t need = sphrt_exact_sort_workspace_bytes(method, n_lists, K);
+    if (need && (!workspace || workspace_size < need))
+        return fail("sort workspace too small: %zu < %zu bytes", workspace_size, need);
+    StreamGuard guard(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(info, 0, (size_t)n_lists * SPHRT_SORT_INFO_FIELDS * sizeof(int64_t), st) !=
+        hipSuccess)
+        return fail("memset failed");
+    GridDev G{};
+    G.K = (int)K;
+    G.nbr = nbr;
+    G.nbe = nbe;
+    const bool inv = invalid != 0;
+    switch (method) {
+    case SPHRT_SORT_SERIAL_AOS:
+        hipLaunchKernelGGL(sort_lists_aos_kernel, dim3((unsigned)n_lists), dim3(64), 0, st, t, reg,
+                           (int)K, (Cand*)workspace, t_out, pay_out);
+        break;
+    case SPHRT_SORT_SERIAL_SOA:
+        launch_sort_lds<SPHRT_SORT_SERIAL_SOA, false, 1>(G, n_lists, t, reg, start, t_out, pay_out,
+                                                         info, st);
+        break;
+    case SPHRT_SORT_WAVE1:
+        if (inv) launch_sort_lds<SPHRT_SORT_WAVE1, true, 1>(G, n_lists, t, reg, start, t_out,
+                                                            pay_out, info, st);
+        else launch_sort_lds<SPHRT_SORT_WAVE1, false, 1>(G, n_lists, t, reg, start, t_out, pay_out,
+                                                         info, st);
+        break;
+    case SPHRT_SORT_WAVE4:
+        if (inv) launch_sort_lds<SPHRT_SORT_WAVE4, true, kExactWaves>(G, n_lists, t, reg, start,
+                                                                      t_out, pay_out, info, st);
+        else launch_sort_lds<SPHRT_SORT_WAVE4, false, kExactWaves>(G, n_lists, t, reg, start,
+                                                                   t_out, pay_out, info, st);
+        break;
+    default:
+        launch_sort_lds<SPHRT_SORT_NETWORK, false, 1>(G, n_lists, t, reg, start, t_out, pay_out,
+                                                      info, st);
+        break;
+    }
+    return check_launch("sort_lists_kernel");
 }

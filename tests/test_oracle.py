@@ -64,6 +64,22 @@ def test_introsort_matches_torch_sort():
         assert np.array_equal(ref.numpy(), got)
 
 
+def test_introsort_matches_torch_sort_at_the_depth_limit():
+    """The same pin on the list families of sort_cases.py, which — unlike the random rows above —
+    reach the depth limit and with it the heapsort (every K here has such ranges; the whole set
+    of K is pinned in test_sort_cases_cpu.py)."""
+    import sort_cases as sc
+    for K in (128, 257, 1024):
+        n_ranges = 0
+        for name, lists in sc.families(K).items():
+            for j, x in enumerate(lists):
+                _, ref = tr.from_numpy(x.copy()).sort()
+                _, got, ranges = oracle.introsort_ranges(x)
+                n_ranges += len(ranges)
+                assert np.array_equal(ref.numpy(), got), f'{name}[{j}] K={K}'
+        assert n_ranges >= 1, K
+
+
 def test_solvers_vs_reference(sqrt_mode):
     z = gc.load('solvers')
     g = oracle.Grid.from_boundaries(z['r_b'], z['e_b'], z['a_b'])
