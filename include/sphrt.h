@@ -616,6 +616,14 @@ int sphrt_trace_normal_fixed_f64(const sphrt_plan *plan, const sphrt_rays *rays,
  * host on a null record, a negative n_elems and (n_elems > 0) a null acc or out. */
 int sphrt_fixed_finalize_f64(const int64_t *acc, int64_t n_elems, const void *scale_rec,
                              double *out, void *stream);
+/* acc element index[i] += terms[i] for i < n under *scale_rec, one thread per term: the device
+ * quantise, split and two integer atomics of the trace entries above (the same device function),
+ * on a caller's list of terms, so that the device arithmetic can be held to the host mirrors below
+ * on chosen inputs.  Nothing is added when the record's flags are non-zero, as in the trace.
+ * Every index[i] must name an element of acc (device memory: not checked).  Fails on the host on a
+ * null record, a negative n and (n > 0) null terms, index or acc. */
+int sphrt_fixed_accumulate_f64(const double *terms, const int64_t *index, int64_t n,
+                               const void *scale_rec, int64_t *acc, void *stream);
 /* Host-only mirrors of the arithmetic above (the same functions the kernels compile), for tests
  * and callers that need to predict bits.  sphrt_fixed_exponent_host: E and flags of a bound
  * (fails on a negative bound or a null output); sphrt_fixed_quantise_host: lo_hi = the split

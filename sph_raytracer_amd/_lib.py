@@ -149,6 +149,7 @@ _SIGNATURES = [
                                              c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
                                              ctypes.c_size_t, c_vp]),
     ('sphrt_fixed_finalize_f64', c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    ('sphrt_fixed_accumulate_f64', c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     ('sphrt_fixed_exponent_host', c_int, [c_dbl, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     ('sphrt_fixed_quantise_host', None, [c_dbl, c_i32, ctypes.POINTER(c_i64)]),
     ('sphrt_fixed_value_host', c_dbl, [c_i64, c_i64, c_i32, c_i32]),

@@ -1,6 +1,7 @@
 // fixed.hip — the scale record and the finalize pass of the fixed-point accumulator (fixed.hpp),
 // and the host mirrors of its arithmetic.  The adds themselves are the trace's (trace.hip,
-// MODE_SCATTER_FIXED / MODE_NORMAL_FIXED).
+// MODE_SCATTER_FIXED / MODE_NORMAL_FIXED); sphrt_fixed_accumulate_f64 runs the same device add on
+// a caller's list of terms.
 #include "common.hpp"
 #include "fixed.hpp"
 
@@ -48,6 +49,17 @@ __global__ __launch_bounds__(256) void fixed_finalize_kernel(const longlong2* __
     out[i] = fixed_value((int64_t)v.x, (int64_t)v.y, s);
 }
 
+// acc element index[i] += terms[i], one thread per term, as the trace adds a segment's term
+// (fixed_accumulate); nothing when the record's flags are set.
+__global__ __launch_bounds__(256) void fixed_accumulate_kernel(const double* __restrict__ terms,
+                                                               const int64_t* __restrict__ index,
+                                                               int64_t n, const int32_t* rec,
+                                                               int64_t* acc) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || rec[1] != 0) return;
+    fixed_accumulate(acc, index[i], terms[i], kFixedBits - rec[0]);
+}
+
 }  // namespace sphrt
 
 using namespace sphrt;
@@ -89,6 +101,21 @@ extern "C" int sphrt_fixed_finalize_f64(const int64_t* acc, int64_t n_elems, con
                        (hipStream_t)stream, reinterpret_cast<const longlong2*>(acc), n_elems,
                        reinterpret_cast<const int32_t*>(scale_rec), out);
     return check_launch("fixed_finalize_kernel");
+}
+
+extern "C" int sphrt_fixed_accumulate_f64(const double* terms, const int64_t* index, int64_t n,
+                                          const void* scale_rec, int64_t* acc, void* stream) {
+    if (!scale_rec) return fail("null scale record");
+    if (n < 0) return fail("negative accumulate length");
+    if (n == 0) return 0;
+    if (!terms || !index || !acc) return fail("null accumulate argument (terms, index or acc)");
+    const int64_t blocks = (n + 255) / 256;
+    if (blocks > INT32_MAX) return fail("accumulate too large");
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(fixed_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, terms, index, n,
+                       reinterpret_cast<const int32_t*>(scale_rec), acc);
+    return check_launch("fixed_accumulate_kernel");
 }
 
 extern "C" int sphrt_fixed_exponent_host(double bound, int32_t* E, int32_t* flags) {

@@ -69,6 +69,17 @@ __host__ __device__ inline void fixed_quantise(double term, int shift, int64_t& 
     lo = (int64_t)(k - h * 4294967296.0);
 }
 
+// acc element idx += term, on the device: the term in quanta of 2^-shift, split, as two 64-bit
+// integer atomics without return on the element's {lo, hi} pair (the trace's *_FIXED adds and
+// sphrt_fixed_accumulate_f64).
+__device__ __forceinline__ void fixed_accumulate(int64_t* acc, int64_t idx, double term, int shift) {
+    int64_t lo, hi;
+    fixed_quantise(term, shift, lo, hi);
+    unsigned long long* p = reinterpret_cast<unsigned long long*>(acc) + 2 * idx;
+    atomicAdd(p, (unsigned long long)lo);
+    atomicAdd(p + 1, (unsigned long long)hi);
+}
+
 __host__ __device__ inline int fixed_clz64(uint64_t x) {   // x != 0
 #if defined(__HIP_DEVICE_COMPILE__)
     return __clzll((long long)x);

@@ -465,15 +465,11 @@ __device__ __forceinline__ FixedAdd fixed_add_of(const TraceOut<T>& o) {
 }
 
 // acc[idx] += term: one float64 atomic, or (*_FIXED) the term in quanta, split, as two 64-bit
-// integer atomics without return on the element's {lo, hi} pair.
+// integer atomics without return on the element's {lo, hi} pair (fixed.hpp fixed_accumulate).
 template <int MODE>
 __device__ __forceinline__ void acc_add(double* acc, int64_t idx, double term, const FixedAdd& f) {
     if constexpr (mode_fixed(MODE)) {
-        int64_t lo, hi;
-        fixed_quantise(term, f.shift, lo, hi);
-        unsigned long long* p = reinterpret_cast<unsigned long long*>(acc) + 2 * idx;
-        atomicAdd(p, (unsigned long long)lo);
-        atomicAdd(p + 1, (unsigned long long)hi);
+        fixed_accumulate(reinterpret_cast<int64_t*>(acc), idx, term, f.shift);
     } else {
         atomicAdd(acc + idx, term);
     }

@@ -1,6 +1,6 @@
 """Host side of the deterministic matrix-free adjoint (csrc/fixed.hpp; sphrt_fixed_scale_f64,
-sphrt_trace_backproject_fixed_f64, sphrt_trace_normal_fixed_f64, sphrt_fixed_finalize_f64 and the
-three host mirrors): the entries are declared, exported and bound; their refusals fire on the
+sphrt_trace_backproject_fixed_f64, sphrt_trace_normal_fixed_f64, sphrt_fixed_finalize_f64,
+sphrt_fixed_accumulate_f64 and the three host mirrors): the entries are declared, exported and bound; their refusals fire on the
 host, before any device call; the fixed-point arithmetic equals Python's integers and
 float(int) bit for bit; the Python layer has the ``deterministic`` switches and still raises
 layout errors before it looks for a device.  (No compute call: no GPU here.)"""
@@ -14,17 +14,19 @@ from fractions import Fraction
 import pytest
 import torch as tr
 
+from fixed_cases import EXPONENTS, _pairs, _terms
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {                                   # name -> argument count
     'sphrt_fixed_scale_f64': 8,
     'sphrt_trace_backproject_fixed_f64': 12,
     'sphrt_trace_normal_fixed_f64': 15,
     'sphrt_fixed_finalize_f64': 5,
+    'sphrt_fixed_accumulate_f64': 6,
     'sphrt_fixed_exponent_host': 3,
     'sphrt_fixed_quantise_host': 3,
     'sphrt_fixed_value_host': 4,
 }
-EXPONENTS = (-1070, -60, 0, 1, 61, 900)
 
 
 def _bits(v):
@@ -151,6 +153,7 @@ def test_scale_and_finalize_refusals_on_the_host():
     lib = _lib()
     p = ctypes.c_void_p(16)
     scale, fin = lib.sphrt_fixed_scale_f64, lib.sphrt_fixed_finalize_f64
+    add = lib.sphrt_fixed_accumulate_f64
     _check(lib, [
         (lambda: scale(p, 4, 1.0, None, 0, 0.0, None, None), b'scale record'),
         (lambda: scale(p, -1, 1.0, None, 0, 0.0, p, None), b'negative scale length'),
@@ -164,6 +167,11 @@ def test_scale_and_finalize_refusals_on_the_host():
         (lambda: fin(p, -1, p, p, None), b'negative finalize length'),
         (lambda: fin(None, 4, p, p, None), b'acc or out'),
         (lambda: fin(p, 4, p, None, None), b'acc or out'),
+        (lambda: add(p, p, 4, None, p, None), b'scale record'),
+        (lambda: add(p, p, -1, p, p, None), b'negative accumulate length'),
+        (lambda: add(None, p, 4, p, p, None), b'terms, index or acc'),
+        (lambda: add(p, None, 4, p, p, None), b'terms, index or acc'),
+        (lambda: add(p, p, 4, p, None, None), b'terms, index or acc'),
     ])
     E, flags = ctypes.c_int32(), ctypes.c_int32()
     _check(lib, [(lambda: lib.sphrt_fixed_exponent_host(-1.0, E, flags), b'negative bound'),
@@ -218,23 +226,6 @@ def test_flags():
         assert math.isnan(lib.sphrt_fixed_value_host(lo, hi, 0, 3))
 
 
-def _terms(E):
-    """Terms under a bound B = 2^E (1 - 2^-53)-ish: zero, the bound's neighbours, exact
-    half-quantum ties on both parities, subnormals and values below half a quantum."""
-    q = Fraction(2) ** (E - 61)
-    out = [0.0, -0.0]
-    top = math.ldexp(1 - 2.0 ** -53, E) if E - 53 >= -1074 else math.ldexp(0.75, E)
-    out += [top, -top, math.ldexp(0.5, E), -math.ldexp(0.5, E)]
-    for k in (0, 1, 2, 3, 4, 5, 2 ** 20, 2 ** 20 + 1, 2 ** 40 + 2, 2 ** 40 + 3, 2 ** 51, 2 ** 51 + 1):
-        tie = (k + Fraction(1, 2)) * q                 # k even: rounds to k; odd: to k + 1
-        for v in (tie, tie + q / 8, tie - q / 8, k * q, q / 2, q / 4, q * 3 / 8, q / 2 ** 30):
-            f = float(v)
-            if Fraction(f) == v and abs(f) <= top:     # (exactly representable ones only)
-                out += [f, -f]
-    out += [5e-324, -5e-324, 2.2250738585072014e-308 / 4, 2.2250738585072014e-308]
-    return [t for t in out if abs(t) <= top]
-
-
 @pytest.mark.parametrize('E', EXPONENTS)
 def test_quantise_equals_python_integers(E):
     lib = _lib()
@@ -273,28 +264,6 @@ def test_terms_above_the_bound_stay_exact(E):
             assert 0 <= lo < 2 ** 32 and hi * 2 ** 32 + lo == want, (E, mult, sign)
             got = lib.sphrt_fixed_value_host(lo, hi, E, 0)
             assert _bits(got) == _bits(math.ldexp(float(want), E - 61))
-
-
-def _pairs():
-    """(lo, hi) pairs of a carry-save accumulator: |V| > 2^64, negative V, more than 53
-    significant bits, ties and sticky cases of the 64-bit normalisation, lo near 2^62."""
-    out = [(0, 0), (1, 0), (0, 1), (0, -1), (5, -1), (2 ** 32 - 1, 0), (2 ** 32 - 1, -1),
-           (2 ** 62, 0), (2 ** 62 + 1, 2 ** 30), (2 ** 62 - 1, -(2 ** 59)),
-           (2 ** 63 - 1, 2 ** 60 - 1), (2 ** 63 - 1, -(2 ** 60))]
-    for v in (2 ** 53 + 1, 2 ** 54 + 2, 2 ** 54 + 6, 2 ** 64 + 2 ** 11, 2 ** 64 + 3 * 2 ** 11,
-              2 ** 64 + 2 ** 11 + 1, 2 ** 64 + 2 ** 11 - 1, 2 ** 80 + 2 ** 27, 2 ** 80 + 2 ** 27 + 1,
-              2 ** 80 + 3 * 2 ** 27, 2 ** 91 + 2 ** 38 + 2 ** 3, 2 ** 91 - 1, 2 ** 64, 2 ** 64 - 1,
-              2 ** 65 + 2 ** 12, 2 ** 65 + 2 ** 12 + 1, 3 * 2 ** 63 + 2 ** 11 * 3, 2 ** 63,
-              (2 ** 53 + 1) * 2 ** 30 + 1, (2 ** 53 + 3) * 2 ** 38 - 1):
-        for sign in (1, -1):
-            V = sign * v
-            hi = V >> 32                               # the canonical split ...
-            out.append((V - hi * 2 ** 32, hi))
-            hi2 = hi - 2 ** 29                         # ... and one with a large lo
-            lo2 = V - hi2 * 2 ** 32
-            if 0 <= lo2 < 2 ** 63 and -(2 ** 63) <= hi2:
-                out.append((lo2, hi2))
-    return out
 
 
 @pytest.mark.parametrize('E', EXPONENTS)
