@@ -482,6 +482,18 @@ int64_t sphrt_loss_partials(int64_t n);
 int sphrt_sq_residual_f64(const double *yhat, const void *y, int y_is_f64, int64_t n, double scale,
                           const int32_t *order, double *r_scaled, double *partial_sums,
                           void *stream);
+/* sphrt_sq_residual_f64 with per-element factors, for SquareLoss(projection_mask=w) (reference
+ * loss.py:87-110: lam * mean(w * (y - f(d))^2)).  With i = order ? order[j] : j:
+ *   r           = yhat[i] - y[i]
+ *   r_scaled[j] = r * ray_scale[i]
+ *   partial sums of weight[i] * (r * r)      two roundings, the order torch's w * (y - f)**2 takes
+ * ray_scale and weight are float64 arrays of n elements indexed as y is (through `order` when it
+ * is given).  The same grid, the same sphrt_loss_partials(n) partial sums in the same fixed
+ * order.  Fails on the host on n <= 0 and on a null yhat, y, ray_scale, weight, r_scaled or
+ * partial_sums. */
+int sphrt_wsq_residual_f64(const double *yhat, const void *y, int y_is_f64, int64_t n,
+                           const double *ray_scale, const double *weight, const int32_t *order,
+                           double *r_scaled, double *partial_sums, void *stream);
 int sphrt_neg_reg_f64(const double *d, int64_t n, double c_neg, double *g, double *partial_sums,
                       void *stream);
 /* One Adam step on float64 coefficients (torch.optim.Adam(fused=True), amsgrad and maximize off:
@@ -549,6 +561,23 @@ int sphrt_trace_normal_f64(const sphrt_plan *plan, const sphrt_rays *rays,
                            int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
                            double *yhat, int64_t y_chan_stride,
                            double *acc, void *workspace, size_t workspace_size, void *stream);
+/* Weighted least squares: sphrt_trace_normal_f64 with the scalar replaced by a factor per ray and
+ * channel.  ray_scale is laid out exactly as m (channels y_chan_stride apart; with
+ * ray_chan_div > 0 ray i's single value at i):
+ *   yhat[c][i] = sum density[c][vox] * len                 bitwise sphrt_trace_integrate_f64's
+ *   r          = (yhat[c][i] - m[c][i]) * ray_scale[c][i]  two roundings
+ *   acc[c][vox] += r * len                                 one more, then a float64 atomic
+ * so acc receives A^T(ray_scale .* (A density - m)).  The factor is read once per ray and
+ * channel.  A ray whose factor is zero is traced and added like any other (its terms are +-0, or
+ * NaN where its residual is not finite: NaN * 0 is NaN, as in torch).  Refusals as
+ * sphrt_trace_normal_f64, and a null ray_scale; all on the host, before any launch. */
+int sphrt_trace_normal_weighted_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                                    const double *density, const double *m,
+                                    const double *ray_scale,
+                                    int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+                                    double *yhat, int64_t y_chan_stride,
+                                    double *acc, void *workspace, size_t workspace_size,
+                                    void *stream);
 
 /* ---- deterministic no-store adjoint: fixed-point scatter (csrc/fixed.hpp) --------------------
  * The two entries above sum y * len with float64 atomics, so their results differ in the last
@@ -611,6 +640,20 @@ int sphrt_trace_normal_fixed_f64(const sphrt_plan *plan, const sphrt_rays *rays,
                                  double *yhat, int64_t y_chan_stride, int64_t *acc,
                                  const void *scale_rec,
                                  void *workspace, size_t workspace_size, void *stream);
+/* Replaces sphrt_trace_normal_weighted_f64 in the same way: the same yhat, r and r * len, then
+ * quantised under *scale_rec and added as two integer atomics.  The bound of its record:
+ * sphrt_fixed_scale_f64(a = density, fa = S * L * L, b = m, fb = S * L) with S = max|ray_scale|
+ * (the caller's to find; it must be finite) and L the outer diameter, since
+ * |r * len| <= S * (max|density| * L + max|m|) * L.  acc, record, refusals and cost as
+ * sphrt_trace_normal_fixed_f64, and a null ray_scale. */
+int sphrt_trace_normal_weighted_fixed_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                                          const double *density, const double *m,
+                                          const double *ray_scale,
+                                          int64_t n_chan, int64_t chan_stride,
+                                          int64_t ray_chan_div,
+                                          double *yhat, int64_t y_chan_stride, int64_t *acc,
+                                          const void *scale_rec,
+                                          void *workspace, size_t workspace_size, void *stream);
 /* out[j] = the value of element j (acc[2j], acc[2j + 1]) under *scale_rec, one thread per
  * element; what reading the float64 accumulator of the entries it replaces was.  Fails on the
  * host on a null record, a negative n_elems and (n_elems > 0) a null acc or out. */

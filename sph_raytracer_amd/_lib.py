@@ -126,6 +126,8 @@ _SIGNATURES = [
     ('sphrt_gather_f64', c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     ('sphrt_loss_partials', c_i64, [c_i64]),
     ('sphrt_sq_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_dbl, c_vp, c_vp, c_vp, c_vp]),
+    ('sphrt_wsq_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp]),
     ('sphrt_neg_reg_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_vp, c_vp]),
     ('sphrt_adam_neg_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl,
                                    c_dbl, c_dbl, c_vp, ctypes.POINTER(CSR), c_vp]),
@@ -141,6 +143,9 @@ _SIGNATURES = [
     ('sphrt_trace_normal_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_dbl,
                                        c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
                                        ctypes.c_size_t, c_vp]),
+    ('sphrt_trace_normal_weighted_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_vp,
+                                                c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                                ctypes.c_size_t, c_vp]),
     ('sphrt_fixed_scale_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_i64, c_dbl, c_vp, c_vp]),
     ('sphrt_trace_backproject_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_i64,
                                                   c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
@@ -148,6 +153,9 @@ _SIGNATURES = [
     ('sphrt_trace_normal_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_dbl,
                                              c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
                                              ctypes.c_size_t, c_vp]),
+    ('sphrt_trace_normal_weighted_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp,
+                                                      c_vp, c_i64, c_i64, c_i64, c_vp, c_i64,
+                                                      c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     ('sphrt_fixed_finalize_f64', c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     ('sphrt_fixed_accumulate_f64', c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     ('sphrt_fixed_exponent_host', c_int, [c_dbl, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),

@@ -56,6 +56,25 @@ __global__ __launch_bounds__(kLossThreads) void sq_residual_kernel(
     block_partial(acc, part);
 }
 
+// The same with per-element factors (SquareLoss(projection_mask=w): lam * mean(w * (y - f(d))^2)):
+// r_scaled[j] = r * ray_scale[i] (i = order[j], as y) and partial sums of weight[i] * (r * r) —
+// two roundings, the order torch's mask * (y - f)**2 takes.  The same grid, strides and tree.
+template <typename TY>
+__global__ __launch_bounds__(kLossThreads) void wsq_residual_kernel(
+    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n,
+    const double* __restrict__ ray_scale, const double* __restrict__ weight,
+    const int32_t* __restrict__ order, double* __restrict__ r_scaled, double* __restrict__ part) {
+    double acc = 0.0;
+    for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
+         j += (int64_t)gridDim.x * kLossThreads) {
+        const int64_t i = order ? (int64_t)order[j] : j;
+        const double r = yhat[i] - (double)y[i];
+        r_scaled[j] = r * ray_scale[i];
+        acc += weight[i] * (r * r);
+    }
+    block_partial(acc, part);
+}
+
 // g -= c_neg where d < 0 (g.sub_(d.lt(0), alpha=c): g - c * 0 is g itself, signed zeros
 // included); partial sums of |clamp(d, max=0)| (NaN stays NaN).
 __global__ __launch_bounds__(kLossThreads) void neg_reg_kernel(
@@ -184,6 +203,26 @@ extern "C" int sphrt_sq_residual_f64(const double* yhat, const void* y, int y_is
         hipLaunchKernelGGL(sq_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
                            st, yhat, (const float*)y, n, scale, order, r_scaled, partial_sums);
     return check_launch("sq_residual");
+}
+
+extern "C" int sphrt_wsq_residual_f64(const double* yhat, const void* y, int y_is_f64, int64_t n,
+                                      const double* ray_scale, const double* weight,
+                                      const int32_t* order, double* r_scaled,
+                                      double* partial_sums, void* stream) {
+    if (n <= 0) return fail("sphrt_wsq_residual_f64: empty measurement");
+    if (!yhat || !y || !ray_scale || !weight || !r_scaled || !partial_sums)
+        return fail("null buffer");
+    StreamGuard guard(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (y_is_f64)
+        hipLaunchKernelGGL(wsq_residual_kernel<double>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                           st, yhat, (const double*)y, n, ray_scale, weight, order, r_scaled,
+                           partial_sums);
+    else
+        hipLaunchKernelGGL(wsq_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                           st, yhat, (const float*)y, n, ray_scale, weight, order, r_scaled,
+                           partial_sums);
+    return check_launch("wsq_residual");
 }
 
 extern "C" int sphrt_neg_reg_f64(const double* d, int64_t n, double c_neg, double* g,

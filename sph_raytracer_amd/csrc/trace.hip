@@ -53,10 +53,17 @@ namespace sphrt {
 // consume_list for a wave with the compacted list in LDS (trace_one, exact_walk_wave), exact_walk
 // for the one lane that streams a sorted list from the workspace.
 enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4,
-       MODE_SCATTER = 5, MODE_NORMAL = 6, MODE_SCATTER_FIXED = 7, MODE_NORMAL_FIXED = 8 };
+       MODE_SCATTER = 5, MODE_NORMAL = 6, MODE_SCATTER_FIXED = 7, MODE_NORMAL_FIXED = 8,
+       MODE_NORMAL_W = 9, MODE_NORMAL_W_FIXED = 10 };
 constexpr bool mode_scatter(int m) { return m == MODE_SCATTER || m == MODE_SCATTER_FIXED; }
-constexpr bool mode_normal(int m) { return m == MODE_NORMAL || m == MODE_NORMAL_FIXED; }
-constexpr bool mode_fixed(int m) { return m == MODE_SCATTER_FIXED || m == MODE_NORMAL_FIXED; }
+// (the weighted normal modes: the residual's factor per ray and channel, TraceOut::ray_scale)
+constexpr bool mode_weighted(int m) { return m == MODE_NORMAL_W || m == MODE_NORMAL_W_FIXED; }
+constexpr bool mode_normal(int m) {
+    return m == MODE_NORMAL || m == MODE_NORMAL_FIXED || mode_weighted(m);
+}
+constexpr bool mode_fixed(int m) {
+    return m == MODE_SCATTER_FIXED || m == MODE_NORMAL_FIXED || m == MODE_NORMAL_W_FIXED;
+}
 constexpr int kNone = 0x7fffffff;  // "no update" in the forward-fill scans
 constexpr int kWavesPerBlock = 4;
 
@@ -443,7 +450,10 @@ struct TraceOut {
     unsigned long long* n_heap;      // workspace: depth-limit ranges, rank-sorted / heap-sorted
     int wedge;                       // solve only the half-planes of a line's azimuth wedge
     const double* meas;       // NORMAL: the measurements, laid out as out (out_chan_stride apart)
-    double scale;             // NORMAL: the residual's factor
+    union {                   // NORMAL: the residual's factor —
+        double scale;             // the call's scalar, or
+        const double* ray_scale;  // (NORMAL_W*) one per ray and channel, laid out as meas.  One
+    };                            // slot: the kernel arguments of the other modes do not move
     const int32_t* fixed_rec; // *_FIXED: the scale record {E, flags, pad}; acc is then the
                               // int64 {lo, hi} pairs, 2 * chan_stride int64 per channel
 };
@@ -513,6 +523,14 @@ __device__ __forceinline__ int64_t ray_index(const TraceOut<T>& o, int64_t c, in
     return (o.ray_chan_div > 0 ? 0 : c) * o.out_chan_stride + ray;
 }
 
+// NORMAL: the factor of the residual of the per-ray element rc (ray_index): the call's scalar, or
+// (NORMAL_W*) that element's own.  A zero factor is a factor like any other: NaN * 0 stays NaN.
+template <int MODE, typename T>
+__device__ __forceinline__ double residual_factor(const TraceOut<T>& o, int64_t rc) {
+    if constexpr (mode_weighted(MODE)) return o.ray_scale[rc];
+    else return o.scale;
+}
+
 // The segment sink: what every wave-level path does with a ray's list once it is compacted —
 // (seg_vox, seg_len), nseg of them in LDS, and the head segment (hlen in voxel hvox, when `head`).
 //   COUNT        the count.
@@ -523,7 +541,8 @@ __device__ __forceinline__ int64_t ray_index(const TraceOut<T>& o, int64_t c, in
 //                out is bitwise INTEGRATE's.  The write of out, by lane 0.  The scatter (SCATTER,
 //                NORMAL): acc[c][vox] += w * len, one acc_add per segment, with w the ray's y
 //                (SCATTER) or the residual (sum - m) * scale (NORMAL; wave_sum leaves the sum in
-//                every lane; two roundings, sphrt_sq_residual_f64's).
+//                every lane; two roundings, sphrt_sq_residual_f64's; NORMAL_W*: scale is
+//                ray_scale[rc], one wave-uniform load per ray and channel, residual_factor).
 template <int MODE, typename T>
 __device__ __forceinline__ void consume_list(const TraceOut<T>& o, int64_t ray, int lane, int nseg,
                                              const int32_t* seg_vox, const double* seg_len,
@@ -558,7 +577,7 @@ __device__ __forceinline__ void consume_list(const TraceOut<T>& o, int64_t ray, 
                 for (int q = lane; q < nseg; q += 64) sum += (double)rho[seg_vox[q]] * seg_len[q];
                 sum = wave_sum(sum);
                 if (lane == 0) o.out[rc] = (T)sum;
-                if constexpr (kScatter) w = (sum - o.meas[rc]) * o.scale;
+                if constexpr (kScatter) w = (sum - o.meas[rc]) * residual_factor<MODE>(o, rc);
             } else {
                 w = (double)o.density[rc];
             }
@@ -1540,8 +1559,10 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
                 for (int64_t c = ch.lo; c < ch.hi; ++c) {
                     const int64_t rc = ray_index(o, c, ray);
                     double w;                                  // the residual, or y
-                    if constexpr (mode_normal(MODE)) w = ((double)o.out[rc] - o.meas[rc]) * o.scale;
-                    else w = (double)o.density[rc];
+                    if constexpr (mode_normal(MODE))
+                        w = ((double)o.out[rc] - o.meas[rc]) * residual_factor<MODE>(o, rc);
+                    else
+                        w = (double)o.density[rc];
                     acc_add<MODE>(o.acc, c * o.chan_stride + vx, w * len, fx);
                 }
             });
@@ -2310,7 +2331,8 @@ template <typename T>
 static TraceOut<T> fused_out(const T* in, int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
                              T* out, int64_t ray_stride, void* acc = nullptr,
                              const double* m = nullptr, double scale = 0.0,
-                             const void* scale_rec = nullptr) {
+                             const void* scale_rec = nullptr,
+                             const double* ray_scale = nullptr) {
     TraceOut<T> o{};
     o.density = in;
     o.n_chan = n_chan;
@@ -2320,7 +2342,8 @@ static TraceOut<T> fused_out(const T* in, int64_t n_chan, int64_t chan_stride, i
     o.out_chan_stride = ray_stride;
     o.acc = static_cast<double*>(acc);
     o.meas = m;
-    o.scale = scale;
+    if (ray_scale) o.ray_scale = ray_scale;
+    else o.scale = scale;
     o.fixed_rec = static_cast<const int32_t*>(scale_rec);
     return o;
 }
@@ -2431,24 +2454,25 @@ static int run_backproject(const sphrt_plan* plan, const sphrt_rays* rays, const
                                              y_chan_stride, acc, nullptr, 0.0, scale_rec),
                            workspace, workspace_size, stream);
 }
+// (NORMAL_W*: the residual's factor is ray_scale, laid out as m, and `scale` is unused)
 template <int MODE>
 static int run_normal(const sphrt_plan* plan, const sphrt_rays* rays, const double* density,
-                      const double* m, double scale, int64_t n_chan, int64_t chan_stride,
-                      int64_t ray_chan_div, double* yhat, int64_t y_chan_stride, void* acc,
-                      const void* scale_rec, void* workspace, size_t workspace_size,
-                      void* stream) {
+                      const double* m, double scale, const double* ray_scale, int64_t n_chan,
+                      int64_t chan_stride, int64_t ray_chan_div, double* yhat,
+                      int64_t y_chan_stride, void* acc, const void* scale_rec, void* workspace,
+                      size_t workspace_size, void* stream) {
     if constexpr (mode_fixed(MODE)) {
         if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
     }
-    if (int e = refuse_fused(plan, rays,
-                             !density || !m || !yhat || !acc
-                                 ? "null normal argument (density, m, yhat or acc)" : nullptr,
-                             n_chan, y_chan_stride, ray_chan_div, chan_stride, workspace,
-                             workspace_size))
+    const char* null_arg = !density || !m || !yhat || !acc
+                               ? "null normal argument (density, m, yhat or acc)" : nullptr;
+    if (mode_weighted(MODE) && !null_arg && !ray_scale) null_arg = "null ray_scale";
+    if (int e = refuse_fused(plan, rays, null_arg, n_chan, y_chan_stride, ray_chan_div,
+                             chan_stride, workspace, workspace_size))
         return e;
     return run_trace<MODE>(plan, rays, nullptr,
                            fused_out(density, n_chan, chan_stride, ray_chan_div, yhat,
-                                     y_chan_stride, acc, m, scale, scale_rec),
+                                     y_chan_stride, acc, m, scale, scale_rec, ray_scale),
                            workspace, workspace_size, stream);
 }
 
@@ -2465,9 +2489,21 @@ extern "C" int sphrt_trace_normal_f64(const sphrt_plan* plan, const sphrt_rays* 
                                       int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
                                       double* yhat, int64_t y_chan_stride, double* acc,
                                       void* workspace, size_t workspace_size, void* stream) {
-    return run_normal<MODE_NORMAL>(plan, rays, density, m, scale, n_chan, chan_stride,
+    return run_normal<MODE_NORMAL>(plan, rays, density, m, scale, nullptr, n_chan, chan_stride,
                                    ray_chan_div, yhat, y_chan_stride, acc, nullptr, workspace,
                                    workspace_size, stream);
+}
+
+extern "C" int sphrt_trace_normal_weighted_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                               const double* density, const double* m,
+                                               const double* ray_scale, int64_t n_chan,
+                                               int64_t chan_stride, int64_t ray_chan_div,
+                                               double* yhat, int64_t y_chan_stride, double* acc,
+                                               void* workspace, size_t workspace_size,
+                                               void* stream) {
+    return run_normal<MODE_NORMAL_W>(plan, rays, density, m, 0.0, ray_scale, n_chan, chan_stride,
+                                     ray_chan_div, yhat, y_chan_stride, acc, nullptr, workspace,
+                                     workspace_size, stream);
 }
 
 extern "C" int sphrt_trace_backproject_fixed_f64(const sphrt_plan* plan, const sphrt_rays* rays,
@@ -2488,9 +2524,19 @@ extern "C" int sphrt_trace_normal_fixed_f64(const sphrt_plan* plan, const sphrt_
                                             int64_t y_chan_stride, int64_t* acc,
                                             const void* scale_rec, void* workspace,
                                             size_t workspace_size, void* stream) {
-    return run_normal<MODE_NORMAL_FIXED>(plan, rays, density, m, scale, n_chan, chan_stride,
-                                         ray_chan_div, yhat, y_chan_stride, acc, scale_rec,
-                                         workspace, workspace_size, stream);
+    return run_normal<MODE_NORMAL_FIXED>(plan, rays, density, m, scale, nullptr, n_chan,
+                                         chan_stride, ray_chan_div, yhat, y_chan_stride, acc,
+                                         scale_rec, workspace, workspace_size, stream);
+}
+
+extern "C" int sphrt_trace_normal_weighted_fixed_f64(
+    const sphrt_plan* plan, const sphrt_rays* rays, const double* density, const double* m,
+    const double* ray_scale, int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+    double* yhat, int64_t y_chan_stride, int64_t* acc, const void* scale_rec, void* workspace,
+    size_t workspace_size, void* stream) {
+    return run_normal<MODE_NORMAL_W_FIXED>(plan, rays, density, m, 0.0, ray_scale, n_chan,
+                                           chan_stride, ray_chan_div, yhat, y_chan_stride, acc,
+                                           scale_rec, workspace, workspace_size, stream);
 }
 
 template <typename F>

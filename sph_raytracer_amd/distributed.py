@@ -180,8 +180,11 @@ def gd(f, y_local, model, coeffs=None, num_iterations=100, loss_fns=None, optim=
         coeffs = tr.ones(model.coeffs_shape, dtype=tr.float64, device=device or f.device)
     coeffs.requires_grad_()
     opt = optim([coeffs], **kwargs)
+    # (a tensor projection_mask, which the single-GPU direct loop takes, is declined here: the
+    # rank's share of a mask over the whole stack is not worked out — the autograd loop)
+    masked = any(isinstance(fn.projection_mask, tr.Tensor) for fn in loss_fns)
     plan = _direct_plan(f.local, y_local, model, coeffs, loss_fns, [coeffs]) \
-        if hasattr(f.local, '_csr') else None
+        if hasattr(f.local, '_csr') and not masked else None
     # the two loops issue different collectives: every rank takes the direct loop or none does
     flag = tr.tensor([1.0 if plan is not None else 0.0], dtype=tr.float64, device=coeffs.device)
     if f._host_staged(flag):

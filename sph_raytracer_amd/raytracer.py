@@ -1069,13 +1069,40 @@ def _gradient_layout(grid, ray_shape, dshape, mshape):
     return n_chan, div, tuple(int(v) for v in mshape)
 
 
-def _launch_normal(parts, grid, d, m, scale, n_chan, div, yhat, acc, dev, fixed=None):
+def _ray_scale(weights, scale, mshape, dev, need_max):
+    """-> (ray_scale, S) of a weighted call: weights (bool, float32 or float64, broadcastable to
+    `mshape`) as float64 times `scale` (one rounding), flat and laid out as the measurements on
+    `dev`; S = max|ray_scale| as a Python float when `need_max` (the fixed-point bound: one
+    readback, a host sync; a non-finite S raises ValueError), else None (nothing read back)."""
+    w = weights.detach().to(dev)
+    rs =(w.to(tr.float64) * float(scale)).expand(tuple(mshape)).reshape(-1).contiguous()
+    return rs, _scale_max(rs) if need_max else None
+
+
+def _scale_max(rs):
+    """max|rs| read back (a host sync); ValueError when it is not finite (the fixed-point bound
+    would poison the whole result)."""
+    S = float(rs.abs().max()) if rs.numel() else 0.0
+    if not math.isfinite(S):
+        raise ValueError('the deterministic weighted gradient needs finite weights (max|weights * '
+                         f'scale| is {S})')
+    return S
+
+
+def _launch_normal(parts, grid, d, m, scale, n_chan, div, yhat, acc, dev, fixed=None,
+                   weighted=None):
     """sphrt_trace_normal_f64 over prebuilt parts: flat float64 d and m on `dev`; yhat receives
     A d, the zeroed acc gains A^T(scale (A d - m)).  With `fixed` (_fixed_buffers, the
     accumulator zeroed) the deterministic form: the scale of |scale| (max|d| L + max|m|) L,
     sphrt_trace_normal_fixed_f64 into the integer accumulator, and its values written to acc
-    (which need not be zeroed); nothing is allocated."""
+    (which need not be zeroed); nothing is allocated.  With `weighted` = (ray_scale, S)
+    (_ray_scale: a flat float64 factor per measurement on `dev`, and its max| | for the fixed
+    form) the weighted entries, sphrt_trace_normal_weighted_f64 / _fixed_f64: ray_scale replaces
+    `scale`, which is then unused, and S |scale| in the bound."""
     plan, batch, ws = parts
+    if weighted is not None:
+        return _launch_normal_weighted(parts, grid, d, m, weighted, n_chan, div, yhat, acc, dev,
+                                       fixed)
     if fixed is not None:
         lib, stream = _lib.load(), _lib.stream_of(dev)
         L, s = _outer_diameter(grid), abs(float(scale))
@@ -1094,19 +1121,47 @@ def _launch_normal(parts, grid, d, m, scale, n_chan, div, yhat, acc, dev, fixed=
         ws.numel(), _lib.stream_of(dev)), 'sphrt_trace_normal_f64')
 
 
-def _fused_gradient(parts, grid, density, m, scale, dev, deterministic=False):
+def _launch_normal_weighted(parts, grid, d, m, weighted, n_chan, div, yhat, acc, dev, fixed):
+    """_launch_normal's weighted form (its arguments; weighted = (ray_scale, S))."""
+    plan, batch, ws = parts
+    rs, S = weighted
+    if rs.numel() != m.numel():
+        raise ValueError(f'{rs.numel()} ray factors for {m.numel()} measurements')
+    lib, stream = _lib.load(), _lib.stream_of(dev)
+    if fixed is not None:
+        L = _outer_diameter(grid)
+        _lib.check(lib.sphrt_fixed_scale_f64(_lib.ptr(d), d.numel(), S * L * L, _lib.ptr(m),
+                                             m.numel(), S * L, _lib.ptr(fixed[1]), stream),
+                   'sphrt_fixed_scale_f64')
+        _lib.check(lib.sphrt_trace_normal_weighted_fixed_f64(
+            plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), _lib.ptr(rs), n_chan,
+            math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(fixed[0]),
+            _lib.ptr(fixed[1]), _lib.ptr(ws), ws.numel(), stream),
+            'sphrt_trace_normal_weighted_fixed_f64')
+        _fixed_finalize(fixed, acc, dev)
+        return
+    _lib.check(lib.sphrt_trace_normal_weighted_f64(
+        plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), _lib.ptr(rs), n_chan,
+        math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(acc), _lib.ptr(ws),
+        ws.numel(), stream), 'sphrt_trace_normal_weighted_f64')
+
+
+def _fused_gradient(parts, grid, density, m, scale, dev, deterministic=False, weights=None):
     """(A density, A^T(scale (A density - m))) from one trace over prebuilt parts, computed in
-    float64 and returned in density's dtype on density's device."""
+    float64 and returned in density's dtype on density's device.  With `weights` the factor is
+    weights * scale per measurement (_ray_scale)."""
     n_chan, div, out_shape = _gradient_layout(grid, parts[1].shape, density.shape, m.shape)
     d, mv = _to_f64(density, dev), _to_f64(m, dev)
+    weighted = None if weights is None else _ray_scale(weights, scale, m.shape, dev, deterministic)
     yhat = tr.empty(mv.numel(), dtype=tr.float64, device=dev)
     if deterministic:
         acc = tr.empty(d.numel(), dtype=tr.float64, device=dev)
         _launch_normal(parts, grid, d, mv, float(scale), n_chan, div, yhat, acc, dev,
-                       _fixed_buffers(d.numel(), dev))
+                       _fixed_buffers(d.numel(), dev), weighted)
     else:
         acc = tr.zeros(d.numel(), dtype=tr.float64, device=dev)
-        _launch_normal(parts, grid, d, mv, float(scale), n_chan, div, yhat, acc, dev)
+        _launch_normal(parts, grid, d, mv, float(scale), n_chan, div, yhat, acc, dev,
+                       weighted=weighted)
     rdt, rdev = density.dtype, density.device
     return (_from_f64(yhat, rdt, dev).reshape(out_shape).to(rdev),
             _from_f64(acc, rdt, dev).reshape(density.shape).to(rdev))
@@ -2133,7 +2188,9 @@ class MatrixFreeOperator:
     element per call and two integer atomics per segment instead of one float64 atomic.  The
     attribute governs ``T``, the backward of ``op(x)``, ``residual_gradient`` and gd()'s loop.
     ``op.residual_gradient(density, m, scale)`` gives ``op(density)`` and
-    ``op.T(scale * (op(density) - m))`` from one trace instead of two.  There are
+    ``op.T(scale * (op(density) - m))`` from one trace instead of two; with ``weights=w`` (a
+    mask, noise weights) ``op.T(w * scale * (op(density) - m))``, still from one trace, and gd()
+    over a ``SquareLoss(projection_mask=w)`` runs its direct loop on that call.  There are
     no ``regs`` / ``lens`` / ``segments`` views: nothing is stored to show.  The workspace is
     shared by the calls: use an operator from one stream at a time."""
 
@@ -2189,11 +2246,22 @@ class MatrixFreeOperator:
         _, _, dshape = _adjoint_layout(self.grid, self._ray_shape, y.shape)
         return self._apply_adjoint(y, dshape, y.dtype, self._rdev)
 
-    def residual_gradient(self, density, measurements, scale=1.0):
+    def residual_gradient(self, density, measurements, scale=1.0, weights=None):
         """-> (yhat, grad) from one trace (sphrt_trace_normal_f64): ``yhat = op(density)`` and
         ``grad = A^T(scale * (yhat - measurements))``, the gradient in ``density`` of
         ``0.5 * scale * ((op(density) - measurements) ** 2).sum()`` — what ``op`` followed by
         ``op.T`` of the residual gives, without tracing the rays a second time.
+
+        ``weights`` (a tensor broadcastable to ``measurements.shape``; bool, float32 or float64,
+        on any device) makes it weighted least squares: ``grad = A^T(ray_scale * (yhat -
+        measurements))`` with ``ray_scale = weights.to(float64) * scale`` (one rounding, formed
+        once on the device), the gradient of ``0.5 * scale * (weights * (op(density) -
+        measurements) ** 2).sum()`` — a mask of bad pixels, 1/sigma^2 noise weights
+        (sphrt_trace_normal_weighted_f64; ``yhat`` is not weighted).  Rays of weight zero are
+        traced like any other: a NaN measurement under a zero weight still gives NaN, as in
+        torch.  With ``op.deterministic`` the fixed-point bound needs max|ray_scale|: one
+        readback per call, a host sync (the atomic mode reads nothing back), and a weight that is
+        not finite raises ValueError.  ``weights=None`` is the unweighted call, unchanged.
 
         ``measurements`` has ``op(density)``'s shape.  Static grids take leading channel axes; a
         dynamic grid pairs time slices with views as the forward does, so ``grad`` is autograd's
@@ -2204,9 +2272,20 @@ class MatrixFreeOperator:
         device.  Not differentiable."""
         density, m = tr.as_tensor(density), tr.as_tensor(measurements)
         _gradient_layout(self.grid, self._ray_shape, density.shape, m.shape)   # (host only)
+        if weights is not None:
+            weights = tr.as_tensor(weights)
+            if weights.dtype not in (tr.bool, tr.float32, tr.float64):
+                raise TypeError(f'weights must be bool, float32 or float64, not {weights.dtype}')
+            try:
+                ok = tuple(tr.broadcast_shapes(weights.shape, m.shape)) == tuple(m.shape)
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f'weights of shape {tuple(weights.shape)} do not broadcast to '
+                                 f'the measurements {tuple(m.shape)}')
         with tr.cuda.device(self._cdev):
             return _fused_gradient(self._parts, self.grid, density, m, scale, self._cdev,
-                                   bool(self.deterministic))
+                                   bool(self.deterministic), weights)
 
     def _fixed_buffers(self):
         """What a deterministic _normal_into adds into: the integer accumulator of a grid.shape
@@ -2214,11 +2293,14 @@ class MatrixFreeOperator:
         with tr.cuda.device(self._cdev):
             return _fixed_buffers(math.prod(self.grid.shape), self._cdev)
 
-    def _normal_into(self, d, m, scale, yhat, acc, fixed=None):
+    def _normal_into(self, d, m, scale, yhat, acc, fixed=None, weighted=None):
         """residual_gradient for gd's fused loop (retrieval._gd_direct): a grid.shape float64
         density and flat float64 measurements on the compute device, into the caller's yhat and
         zeroed acc; nothing allocated.  With ``deterministic`` set, through `fixed` (the caller's
-        _fixed_buffers(), zeroed here; without them a pair is allocated for the call)."""
+        _fixed_buffers(), zeroed here; without them a pair is allocated for the call).  With
+        `weighted` = (ray_scale, S) — a flat float64 factor per measurement and, for the
+        deterministic form, max|ray_scale| as a float, prepared once by the caller — the weighted
+        trace; `scale` is then unused."""
         if self.deterministic:
             if fixed is None:
                 fixed = self._fixed_buffers()
@@ -2226,7 +2308,8 @@ class MatrixFreeOperator:
                 fixed[0].zero_()
         else:
             fixed = None
-        _launch_normal(self._parts, self.grid, d, m, scale, 1, 0, yhat, acc, self._cdev, fixed)
+        _launch_normal(self._parts, self.grid, d, m, scale, 1, 0, yhat, acc, self._cdev, fixed,
+                       weighted)
 
     def __repr__(self):
         if self.dynamic:

@@ -125,7 +125,8 @@ def _unit(m):
 def _direct_plan(f, y, model, coeffs, loss_fns, optim_vars):
     """The loss terms of a loop `_gd_direct` runs without autograd, or None.  It covers the
     examples/static_retrieval.py loop: a FullyDenseModel (the coefficients are the density) on a
-    static Operator, one SquareLoss and at most one NegRegularizer, scalar weights, no masks, the
+    static Operator, one SquareLoss and at most one NegRegularizer, scalar weights, no masks but
+    the SquareLoss's projection_mask (`_ray_mask`: per-ray weights, a mask of bad pixels), the
     coefficients the only optimised variable.  Anything else takes the autograd loop."""
     from .raytracer import Operator
     if not isinstance(f, Operator) or f.dynamic or f._csr is None or y is None:
@@ -145,6 +146,18 @@ def _fused_plan(f, y, model, coeffs, loss_fns, optim_vars):
     return _loop_terms(f, y, model, coeffs, loss_fns, optim_vars)
 
 
+def _ray_mask(mask, y):
+    """Is `mask` a SquareLoss projection_mask `_gd_direct` weighs the residual with: a constant
+    tensor on y's device, bool, float32 or float64, broadcastable to y's shape."""
+    if not (isinstance(mask, t.Tensor) and mask.device == y.device and not mask.requires_grad
+            and mask.dtype in (t.bool, t.float32, t.float64)):
+        return False
+    try:
+        return tuple(t.broadcast_shapes(mask.shape, y.shape)) == tuple(y.shape)
+    except RuntimeError:
+        return False
+
+
 def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
     """(SquareLoss, NegRegularizer or None) when model, variables, measurements and loss terms
     are those `_gd_direct` runs over the operator `f`, else None."""
@@ -161,7 +174,10 @@ def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
     sq = neg = None
     for fn in loss_fns:
         if not (fn.use_grad and isinstance(fn.lam, (int, float)) and not isinstance(fn.lam, bool)
-                and _unit(fn.projection_mask) and _unit(fn.volume_mask)):
+                and _unit(fn.volume_mask)):
+            return None
+        if not (_unit(fn.projection_mask)
+                or type(fn) is SquareLoss and _ray_mask(fn.projection_mask, y)):
             return None
         if type(fn) is SquareLoss and sq is None:
             sq = fn
@@ -190,6 +206,11 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
 
     Gradient of lam * mean((y - f(d))^2): autograd's chain gives (lam / N) * (2 * (y - f(d)))
     negated, i.e. (f(d) - y) * (2 * (lam / N)) exactly (scaling by 2 and negation are exact).
+    With a projection_mask w (`_ray_mask`), lam * mean(w * (y - f(d))^2): autograd's mul backward
+    weighs the mean's lam / N first, (lam / N) * w_i (one rounding), and the pow backward
+    multiplies by 2 * (y - f(d)) (exact), so the adjoint's input is (f(d) - y) * s with
+    s = ((lam / N) * w) * 2, formed once before the loop; the loss sums w * (r * r)
+    (sphrt_wsq_residual_f64; fused: sphrt_trace_normal_weighted_f64 with ray_scale = s).
     Gradient of lam * mean(|clip(d, max=0)|): -(lam / N) where d < 0, else 0 (sign(0) = 0).
     The two are summed (IEEE addition commutes, so the order autograd accumulates them in does
     not matter) and handed to the optimiser as coeffs.grad.
@@ -239,6 +260,18 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
             y_res, res_order = yd.reshape(-1).index_select(0, f._ray_id_long()), None
     yhat_buf = t.empty(n_meas, dtype=coeffs.dtype, device=coeffs.device) \
         if loop_desc is not None or fused else None
+    # a projection_mask: the loss's weights w and the residual's factors s, once, laid out as the
+    # residual kernel reads y (in trace order where y was permuted above)
+    w_res = s_res = weighted = None
+    if isinstance(sq.projection_mask, t.Tensor):
+        w_res = sq.projection_mask.detach().to(t.float64).expand(yd.shape).contiguous().reshape(-1)
+        s_res = (c_sq * w_res) * 2
+        if keep_rows is not None:
+            w_res, s_res = (v.index_select(0, f._ray_id_long()) for v in (w_res, s_res))
+        if fused:
+            # (a deterministic operator's fixed-point bound: max|s|, read back once for the loop)
+            from .raytracer import _scale_max
+            weighted = (s_res, _scale_max(s_res) if f.deterministic else None)
     # the fused trace subtracts float64 measurements (a float32 y promoted once, exactly)
     m64 = yd.to(t.float64).reshape(-1) if fused else None
     # a deterministic operator's integer accumulator and scale record, once for the whole loop
@@ -269,7 +302,10 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                     # f(d) into yhat_buf and A^T((f(d) - y) * (2 lam / N)) into a zeroed g from
                     # one trace; the residual launch below then only sums the loss
                     g = t.zeros_like(d)
-                    f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed)
+                    if weighted is None:
+                        f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed)
+                    else:
+                        f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed, weighted=weighted)
                     yhat = yhat_buf.view(yd.shape)
                 elif loop_desc is not None:
                     # (staged: the forward reads the brick copy the previous Adam launch wrote;
@@ -287,10 +323,17 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 # r * r (the loss) in one launch (csrc/loss.hip)
                 # (in the trace's ray order when the adjoint takes that: no permutation launch)
                 r_scaled = t.empty_like(yhat)
-                _lib.check(lib.sphrt_sq_residual_f64(
-                    _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
-                    2 * c_sq, _lib.ptr(res_order), _lib.ptr(r_scaled), _lib.ptr(part_sq[it]),
-                    stream), 'sphrt_sq_residual_f64')
+                if w_res is None:
+                    _lib.check(lib.sphrt_sq_residual_f64(
+                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
+                        2 * c_sq, _lib.ptr(res_order), _lib.ptr(r_scaled), _lib.ptr(part_sq[it]),
+                        stream), 'sphrt_sq_residual_f64')
+                else:
+                    # (with a projection_mask: r * s_i, and the partial sums of w_i * (r * r))
+                    _lib.check(lib.sphrt_wsq_residual_f64(
+                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
+                        _lib.ptr(s_res), _lib.ptr(w_res), _lib.ptr(res_order), _lib.ptr(r_scaled),
+                        _lib.ptr(part_sq[it]), stream), 'sphrt_wsq_residual_f64')
                 if not fused:
                     g = f._apply_adjoint(r_scaled, tuple(d.shape), d.dtype, d.device,
                                          trace_order=order is not None)

@@ -7,6 +7,8 @@ trace + scatter) beside the stored-trace Operator, on one GPU.
                                      [--out profiles/matrix_free_gradient_times.json]
     python tools/matrix_free_time.py --deterministic [--configs c2 c3]
                                      [--out profiles/matrix_free_deterministic_times.json]
+    python tools/matrix_free_time.py --weighted [--configs c3] [--gd-config c5] [--base DIR]
+                                     [--out profiles/matrix_free_weighted_times.json]
 
 Per config (bench.py's CONFIGS) two legs, each in a fresh child process with its own time limit
 (a leg that fails or runs out of time ends the run: nothing more is started):
@@ -37,6 +39,21 @@ config, the same child processes and limits):
                op.deterministic False and True (HIP events around `reps` calls, REPEATS
                interleaved rounds, all kept), and the peak of one fused call in each mode.
                Derived: medians, the ratio of the modes and the spread of the repeats.
+
+--weighted measures weighted least squares (one leg per config, then one gd leg; the same child
+processes and limits):
+  weighted     float64, in one process, interleaved rounds: ms per unweighted
+               op.residual_gradient(x, m, s), per weighted call
+               op.residual_gradient(x, m, s, weights=w) with op.deterministic False and True, and
+               per two-call path it replaces, op(x) then op.T(w * s * (op(x) - m)), in both modes.
+               With --base DIR (a checkout of the parent commit with its library built), that
+               tree's own --leg gradient runs in child processes before and after: the unweighted
+               call there, the same box and session.  Derived: the unweighted call here against
+               the parent's repeats and their spread; the weighted call against the two calls;
+  gd_masked    ms per iteration of gd(..., 100) on bench.py's C5 retrieval problem with
+               SquareLoss(projection_mask=a 0/1 mask) + NegRegularizer, over a stored Operator
+               and over a MatrixFreeOperator, through the direct loop and through the autograd
+               loop (the plan functions made to return None), REPEATS times each.
 """
 import argparse
 import json
@@ -208,6 +225,163 @@ def leg_deterministic(config, reps):
     return rec
 
 
+def leg_weighted(config, reps):
+    import torch
+    from sph_raytracer_amd import MatrixFreeOperator
+    grid, geom, dev, xs, ys = _problem(config)
+    ts = dict(time_slices=True) if grid.dynamic else {}
+    x, m = xs[torch.float64], ys[torch.float64]
+    g = torch.Generator(device=dev).manual_seed(1)
+    w = torch.rand(m.shape, dtype=torch.float64, device=dev, generator=g)
+    w[torch.rand(m.shape, device=dev, generator=g) < 0.2] = 0      # a fifth of the rays masked
+    op = MatrixFreeOperator(grid, geom, dynamic=grid.dynamic, device=dev)
+    rec = {'config': config, 'rays': int(op._parts[1].n), 'reps': reps, 'repeats': REPEATS,
+           'dtype': 'float64', 'masked_fraction': float((w == 0).double().mean())}
+
+    def mode(det, fn):
+        def run():
+            op.deterministic = det
+            return fn()
+        return run
+
+    def two_calls():
+        ax = op(x)
+        return ax, op.T((w * 0.5) * (ax - m), **ts)
+
+    legs = [('unweighted_fused_ms', mode(False, lambda: op.residual_gradient(x, m, 0.5)))]
+    for det, tag in ((False, 'atomic'), (True, 'deterministic')):
+        legs += [(f'weighted_fused_ms_{tag}',
+                  mode(det, lambda: op.residual_gradient(x, m, 0.5, weights=w))),
+                 (f'two_calls_ms_{tag}', mode(det, two_calls))]
+    for name, fn in legs:
+        fn()                                                     # warm-up
+        rec[name] = []
+    for _ in range(REPEATS):                                   # interleaved: one of each per round
+        for name, fn in legs:
+            rec[name].append(events_ms(fn, reps))
+    return rec
+
+
+def derive_weighted(g, parent):
+    d = {'unweighted_fused_ms': _median(g['unweighted_fused_ms'])}
+    if parent:
+        p = [v for rec in parent for v in rec['fused_ms']]
+        d['parent_unweighted_fused_ms'] = _median(p)
+        d['parent_spread_ms'] = max(p) - min(p)
+        d['unweighted_minus_parent_ms'] = d['unweighted_fused_ms'] - _median(p)
+        d['unweighted_within_parent_spread'] = bool(
+            min(p) <= d['unweighted_fused_ms'] <= max(p)
+            or abs(d['unweighted_minus_parent_ms']) <= d['parent_spread_ms'])
+    for tag in ('atomic', 'deterministic'):
+        f, t = g[f'weighted_fused_ms_{tag}'], g[f'two_calls_ms_{tag}']
+        spread = max(max(f) - min(f), max(t) - min(t))
+        gain = _median(t) - _median(f)
+        d[f'weighted_fused_ms_{tag}'], d[f'two_calls_ms_{tag}'] = _median(f), _median(t)
+        d[f'gain_ms_{tag}'], d[f'spread_ms_{tag}'] = gain, spread
+        d[f'faster_by_more_than_spread_{tag}'] = bool(gain > spread)
+    return d
+
+
+def leg_gd_masked(config, iterations=100):
+    import torch
+    import bench
+    from sph_raytracer_amd import MatrixFreeOperator, Operator, retrieval
+    from sph_raytracer_amd.loss import NegRegularizer, SquareLoss
+    from sph_raytracer_amd.model import FullyDenseModel
+    grid, geom = bench.build_geometry(bench.CONFIGS[config], 0, 1)
+    dev = torch.device('cuda', 0)
+    truth = torch.zeros(tuple(grid.shape), dtype=torch.float64, device=dev)
+    truth[:, 32:, :32] = 1                       # bench.py's C5 retrieval problem
+    truth[:, :32, 32:] = 1
+    model = FullyDenseModel(grid)
+    ops = {'stored': Operator(grid, geom, device=dev),
+           'matrix_free': MatrixFreeOperator(grid, geom, device=dev)}
+    y = ops['stored'](truth)
+    g = torch.Generator(device=dev).manual_seed(1)
+    mask = (torch.rand(y.shape, device=dev, generator=g) > 0.2).to(torch.float64)
+    plans = retrieval._direct_plan, retrieval._fused_plan
+
+    def none(*a, **k):
+        return None
+
+    rec = {'config': config, 'iterations': iterations, 'repeats': REPEATS,
+           'masked_fraction': float((mask == 0).double().mean())}
+    for kind, op in ops.items():
+        direct, auto, final = [], [], {}
+        for rnd in range(REPEATS + 1):                         # (round 0 warms up, untimed)
+            for name, into, (dp, fp) in (('direct', direct, plans), ('autograd', auto, (none, none))):
+                retrieval._direct_plan, retrieval._fused_plan = dp, fp
+                try:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    _, _, losses = retrieval.gd(
+                        op, y.clone(), model, num_iterations=iterations if rnd else 3, lr=1e-1,
+                        loss_fns=[SquareLoss(projection_mask=mask), NegRegularizer()],
+                        progress_bar=False)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                finally:
+                    retrieval._direct_plan, retrieval._fused_plan = plans
+                if rnd:
+                    into.append(dt * 1e3 / iterations)
+                    final[name] = [v[-1] for v in losses.values()]
+        rec[f'{kind}_direct_ms_per_iteration'] = direct
+        rec[f'{kind}_autograd_ms_per_iteration'] = auto
+        rec[f'{kind}_final_losses_direct'] = final['direct']
+        rec[f'{kind}_final_losses_autograd'] = final['autograd']
+    return rec
+
+
+def derive_gd_masked(g):
+    d = {}
+    for kind in ('stored', 'matrix_free'):
+        f, a = g[f'{kind}_direct_ms_per_iteration'], g[f'{kind}_autograd_ms_per_iteration']
+        spread = max(max(f) - min(f), max(a) - min(a))
+        gain = _median(a) - _median(f)
+        d[kind] = {'direct_ms_per_iteration': _median(f), 'autograd_ms_per_iteration': _median(a),
+                   'gain_ms': gain, 'spread_ms': spread,
+                   'faster_by_more_than_spread': bool(gain > spread)}
+    return d
+
+
+def main_weighted(args):
+    out = {}
+
+    def save():
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            json.dump(out, fh, indent=1)
+            fh.write('\n')
+
+    base_tool = os.path.join(os.path.abspath(args.base), 'tools', os.path.basename(__file__)) \
+        if args.base else None
+    for config in args.configs:
+        parent = []
+        if base_tool:
+            before = _child('gradient', config, args.reps, base_tool)
+            if before is None:
+                return 1
+            parent.append(before)
+        rec = _child('weighted', config, args.reps)
+        if rec is None:
+            return 1
+        if base_tool:
+            again = _child('gradient', config, args.reps, base_tool)
+            if again is None:
+                return 1
+            parent.append(again)
+        out[config] = {'weighted': rec, 'parent_gradient': parent,
+                       'derived': derive_weighted(rec, parent)}
+        save()
+    rec = _child('gd_masked', args.gd_config, None)
+    if rec is None:
+        return 1
+    out[f'gd_{args.gd_config}'] = {'gd_masked': rec, 'derived': derive_gd_masked(rec)}
+    save()
+    print(json.dumps({c: out[c]['derived'] for c in out}))
+    return 0
+
+
 def derive_deterministic(g):
     d = {}
     for what in ('backproject', 'fused'):
@@ -297,10 +471,11 @@ def derive_gd(g):
             'faster_by_more_than_spread': bool(gain > spread)}
 
 
-def _child(leg, config, reps):
+def _child(leg, config, reps, tool=None):
     """One leg in a fresh process -> its record, or None (reported) when it failed or ran out of
-    time: the caller starts nothing more."""
-    cmd = [sys.executable, os.path.abspath(__file__), '--leg', leg, '--configs', config]
+    time: the caller starts nothing more.  `tool`: another checkout's copy of this script (it
+    imports its own tree)."""
+    cmd = [sys.executable, tool or os.path.abspath(__file__), '--leg', leg, '--configs', config]
     if reps:
         cmd += ['--reps', str(reps)]
     try:
@@ -365,23 +540,33 @@ def main():
                     help='measure the fused residual back-projection and gd over it instead')
     ap.add_argument('--deterministic', action='store_true',
                     help='measure the fixed-point adjoint beside the float64-atomic one instead')
-    ap.add_argument('--gd-config', default='c5', help='the gd leg\'s problem (--gradient)')
-    ap.add_argument('--leg', choices=('matrix_free', 'operator', 'gradient', 'gd', 'deterministic'),
+    ap.add_argument('--weighted', action='store_true',
+                    help='measure the weighted gradient and gd with a projection mask instead')
+    ap.add_argument('--base', default=None,
+                    help='--weighted: a checkout of the parent commit, its library built')
+    ap.add_argument('--gd-config', default='c5',
+                    help='the gd leg\'s problem (--gradient, --weighted)')
+    ap.add_argument('--leg', choices=('matrix_free', 'operator', 'gradient', 'gd', 'deterministic',
+                                      'weighted', 'gd_masked'),
                     help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'matrix_free_deterministic_times.json'
+        args.out = os.path.join(ROOT, 'profiles', 'matrix_free_weighted_times.json'
+                                if args.weighted else 'matrix_free_deterministic_times.json'
                                 if args.deterministic else 'matrix_free_gradient_times.json'
                                 if args.gradient else 'matrix_free_times.json')
-    if args.leg == 'gd':
-        print(json.dumps(leg_gd(args.configs[0])))
+    if args.leg in ('gd', 'gd_masked'):
+        print(json.dumps((leg_gd if args.leg == 'gd' else leg_gd_masked)(args.configs[0])))
         return 0
     if args.leg:
         reps = args.reps or (5 if args.configs[0] == 'c3' else 20)
         fn = {'matrix_free': leg_matrix_free, 'operator': leg_operator,
-              'gradient': leg_gradient, 'deterministic': leg_deterministic}[args.leg]
+              'gradient': leg_gradient, 'deterministic': leg_deterministic,
+              'weighted': leg_weighted}[args.leg]
         print(json.dumps(fn(args.configs[0], reps)))
         return 0
+    if args.weighted:
+        return main_weighted(args)
     if args.deterministic:
         return main_deterministic(args)
     if args.gradient:
