@@ -494,6 +494,33 @@ int sphrt_sq_residual_f64(const double *yhat, const void *y, int y_is_f64, int64
 int sphrt_wsq_residual_f64(const double *yhat, const void *y, int y_is_f64, int64_t n,
                            const double *ray_scale, const double *weight, const int32_t *order,
                            double *r_scaled, double *partial_sums, void *stream);
+/* The robust residuals: psi of the residual in the residual's place (AbsLoss, reference
+ * loss.py: lam * mean(w * |y - f(d)|); HuberLoss: lam * mean(w * huber_loss(f(d), y, delta))). */
+#define SPHRT_RESID_ABS   1   /* psi(r) = sign(r): -1, 0, +1                      */
+#define SPHRT_RESID_HUBER 2   /* psi(r) = r clamped to [-delta, delta], delta > 0  */
+/* sphrt_wsq_residual_f64 for a robust loss: the same grid, the same sphrt_loss_partials(n)
+ * partial sums in the same fixed order, the same use of `order`.  With i = order ? order[j] : j:
+ *   r           = yhat[i] - y[i]                      one rounding (a float32 y promoted exactly)
+ *   r_scaled[j] = psi(r) * ray_scale[i]               one rounding; exact for ABS
+ *   ABS    partial sums of weight[i] * |r|            one rounding
+ *   HUBER  partial sums of weight[i] * h(r), z = |r|,
+ *          h = z < delta ? (0.5 * z) * z : delta * (z - 0.5 * delta)
+ *                                                     torch's huber_loss forward, op by op
+ * Every elementwise value is the one torch's elementwise ops give on the device (tested against
+ * torch on an MI355X, tests/test_gpu_robust_gradient.py): sign(r) is (0 < r) - (r < 0), so a
+ * residual of +-0 or NaN has psi = +0 under ABS — autograd's abs backward also gives a NaN
+ * residual a zero gradient on the device, as on the CPU — and |NaN| = NaN in the sum; under HUBER
+ * a NaN residual fails both compares, so psi, h and the sum are NaN, as torch's huber_loss
+ * forward and backward give; +-inf is +-1 or +-delta with an infinite sum; denormals are not
+ * flushed.  r_scaled is bitwise torch.sign(r) * ray_scale and torch.clamp(r, -delta, delta) *
+ * ray_scale; against autograd's own chain the only difference is the sign of a zero under ABS
+ * (autograd negates sign(y - f) * s, this forms sign(f - y) * s).  `delta` is unused for ABS.
+ * Fails on the host on an unknown kind, for HUBER on a delta that is not finite and > 0, on
+ * n <= 0 and on a null yhat, y, ray_scale, weight, r_scaled or partial_sums. */
+int sphrt_robust_residual_f64(const double *yhat, const void *y, int y_is_f64, int64_t n,
+                              int kind, double delta,
+                              const double *ray_scale, const double *weight, const int32_t *order,
+                              double *r_scaled, double *partial_sums, void *stream);
 int sphrt_neg_reg_f64(const double *d, int64_t n, double c_neg, double *g, double *partial_sums,
                       void *stream);
 /* One Adam step on float64 coefficients (torch.optim.Adam(fused=True), amsgrad and maximize off:
@@ -578,6 +605,27 @@ int sphrt_trace_normal_weighted_f64(const sphrt_plan *plan, const sphrt_rays *ra
                                     double *yhat, int64_t y_chan_stride,
                                     double *acc, void *workspace, size_t workspace_size,
                                     void *stream);
+/* Robust fidelity: sphrt_trace_normal_weighted_f64 with psi of the residual (SPHRT_RESID_*; the
+ * sign for ABS, the clamp to +-delta for HUBER) in the residual's place:
+ *   yhat[c][i] = sum density[c][vox] * len          bitwise sphrt_trace_integrate_f64's
+ *   r          = yhat[c][i] - m[c][i]               one rounding
+ *   w          = psi(r) * ray_scale[c][i]           one rounding; exact for ABS
+ *   acc[c][vox] += w * len                          one more, then a float64 atomic
+ * so acc receives A^T(ray_scale .* psi(A density - m)).  psi is sphrt_robust_residual_f64's,
+ * special values included: a residual of +-0 (or, under ABS, NaN) has w = +-0 and adds nothing;
+ * under HUBER a NaN residual adds NaN.  psi and the factor are formed once per ray and channel
+ * (the lane-serial exact walk re-forms them per segment, as it re-reads the residual).
+ * ray_scale is laid out as m and is always an array: a caller with one scalar expands it once.
+ * Channels, ray_chan_div, a miss (yhat = 0, nothing added) and the workspace as the weighted
+ * entry's.  `delta` is unused for ABS.  Refusals, all on the host before any launch: an unknown
+ * kind, for HUBER a delta that is not finite and > 0, then sphrt_trace_normal_weighted_f64's. */
+int sphrt_trace_normal_robust_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                                  const double *density, const double *m,
+                                  const double *ray_scale, int kind, double delta,
+                                  int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+                                  double *yhat, int64_t y_chan_stride,
+                                  double *acc, void *workspace, size_t workspace_size,
+                                  void *stream);
 
 /* ---- deterministic no-store adjoint: fixed-point scatter (csrc/fixed.hpp) --------------------
  * The two entries above sum y * len with float64 atomics, so their results differ in the last
@@ -654,6 +702,23 @@ int sphrt_trace_normal_weighted_fixed_f64(const sphrt_plan *plan, const sphrt_ra
                                           double *yhat, int64_t y_chan_stride, int64_t *acc,
                                           const void *scale_rec,
                                           void *workspace, size_t workspace_size, void *stream);
+/* Replaces sphrt_trace_normal_robust_f64 in the same way: the same yhat, r, w and w * len, then
+ * quantised under *scale_rec and added as two integer atomics.  The bound of its record needs no
+ * host read of max|ray_scale|: sphrt_fixed_scale_f64(a = ray_scale, na, fa, b = NULL, 0, 0) with
+ * fa = L for ABS and fa = delta * L for HUBER, L = 2 * r_b[nr] the outer diameter, since
+ * |psi| <= 1 or delta and so |w * len| <= max|ray_scale| * fa (a ray_scale that is not finite
+ * poisons the record: every value NaN).  As for the entries above, a head segment longer than L
+ * is still quantised and added exactly, up to 2^32 times the bound.  acc, record, refusals and
+ * cost as sphrt_trace_normal_weighted_fixed_f64, and sphrt_trace_normal_robust_f64's of kind and
+ * delta. */
+int sphrt_trace_normal_robust_fixed_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                                        const double *density, const double *m,
+                                        const double *ray_scale, int kind, double delta,
+                                        int64_t n_chan, int64_t chan_stride,
+                                        int64_t ray_chan_div,
+                                        double *yhat, int64_t y_chan_stride, int64_t *acc,
+                                        const void *scale_rec,
+                                        void *workspace, size_t workspace_size, void *stream);
 /* out[j] = the value of element j (acc[2j], acc[2j + 1]) under *scale_rec, one thread per
  * element; what reading the float64 accumulator of the entries it replaces was.  Fails on the
  * host on a null record, a negative n_elems and (n_elems > 0) a null acc or out. */

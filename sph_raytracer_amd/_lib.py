@@ -128,6 +128,8 @@ _SIGNATURES = [
     ('sphrt_sq_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     ('sphrt_wsq_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp]),
+    ('sphrt_robust_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp]),
     ('sphrt_neg_reg_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_vp, c_vp]),
     ('sphrt_adam_neg_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl,
                                    c_dbl, c_dbl, c_vp, ctypes.POINTER(CSR), c_vp]),
@@ -146,6 +148,9 @@ _SIGNATURES = [
     ('sphrt_trace_normal_weighted_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_vp,
                                                 c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
                                                 ctypes.c_size_t, c_vp]),
+    ('sphrt_trace_normal_robust_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_vp,
+                                              c_int, c_dbl, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp,
+                                              c_vp, ctypes.c_size_t, c_vp]),
     ('sphrt_fixed_scale_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_i64, c_dbl, c_vp, c_vp]),
     ('sphrt_trace_backproject_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_i64,
                                                   c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
@@ -156,6 +161,10 @@ _SIGNATURES = [
     ('sphrt_trace_normal_weighted_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp,
                                                       c_vp, c_i64, c_i64, c_i64, c_vp, c_i64,
                                                       c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    ('sphrt_trace_normal_robust_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp,
+                                                    c_vp, c_int, c_dbl, c_i64, c_i64, c_i64, c_vp,
+                                                    c_i64, c_vp, c_vp, c_vp, ctypes.c_size_t,
+                                                    c_vp]),
     ('sphrt_fixed_finalize_f64', c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     ('sphrt_fixed_accumulate_f64', c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     ('sphrt_fixed_exponent_host', c_int, [c_dbl, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),

@@ -63,6 +63,27 @@ struct StreamGuard {
     explicit StreamGuard(void* stream) : g(stream_device(stream)) {}
 };
 
+// The robust residuals (SPHRT_RESID_*): psi of the residual r, shared by the trace's sink and the
+// loss tail.  delta > 0: r clamped to [-delta, delta] (HUBER; a NaN fails both compares and
+// passes through, as in torch's huber_loss backward).  delta == 0: the sign of r, -1, 0 or +1
+// (ABS; +-0 and NaN give +0: torch.sign's (0 < r) - (r < 0)).
+__device__ __forceinline__ double robust_psi(double r, double delta) {
+    if (delta > 0.0) return r < -delta ? -delta : (r > delta ? delta : r);
+    return (double)((int)(0.0 < r) - (int)(r < 0.0));
+}
+// The robust entries' own host refusals: an unknown kind, and for HUBER a delta that is not
+// finite and > 0.  -> the delta robust_psi takes in `rd` (0 for ABS).
+inline int refuse_robust(int kind, double delta, double& rd) {
+    rd = 0.0;
+    if (kind == SPHRT_RESID_ABS) return 0;
+    if (kind != SPHRT_RESID_HUBER)
+        return fail("unknown residual kind %d (SPHRT_RESID_ABS or SPHRT_RESID_HUBER)", kind);
+    if (!(delta > 0.0) || __builtin_isinf(delta))   // (a NaN fails the compare)
+        return fail("the Huber delta must be finite and > 0, not %g", delta);
+    rd = delta;
+    return 0;
+}
+
 // Validate plan + batch and convert to the by-value kernel argument forms.
 inline int resolve(const sphrt_plan* plan, const sphrt_rays* rays, GridDev& G, RaysDev& R,
                    void* stream) {

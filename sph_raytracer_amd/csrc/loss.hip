@@ -75,6 +75,31 @@ __global__ __launch_bounds__(kLossThreads) void wsq_residual_kernel(
     block_partial(acc, part);
 }
 
+// The robust tails (AbsLoss: lam * mean(w * |y - f(d)|); HuberLoss: lam * mean(w * huber(f(d),
+// y))): r_scaled[j] = psi(r) * ray_scale[i] (robust_psi, common.hpp: the sign of r, or r clamped
+// to +-delta) and partial sums of weight[i] * |r| (delta == 0, ABS) or weight[i] * h(r) with
+// z = |r|, h = z < delta ? (0.5 * z) * z : delta * (z - 0.5 * delta) — torch's huber_loss
+// forward, operation by operation (a NaN residual fails the compare and stays NaN).  The same
+// grid, strides and tree.
+template <typename TY>
+__global__ __launch_bounds__(kLossThreads) void robust_residual_kernel(
+    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n, double delta,
+    const double* __restrict__ ray_scale, const double* __restrict__ weight,
+    const int32_t* __restrict__ order, double* __restrict__ r_scaled, double* __restrict__ part) {
+    double acc = 0.0;
+    for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
+         j += (int64_t)gridDim.x * kLossThreads) {
+        const int64_t i = order ? (int64_t)order[j] : j;
+        const double r = yhat[i] - (double)y[i];
+        r_scaled[j] = robust_psi(r, delta) * ray_scale[i];
+        const double z = __builtin_fabs(r);
+        double h = z;
+        if (delta > 0.0) h = z < delta ? (0.5 * z) * z : delta * (z - 0.5 * delta);
+        acc += weight[i] * h;
+    }
+    block_partial(acc, part);
+}
+
 // g -= c_neg where d < 0 (g.sub_(d.lt(0), alpha=c): g - c * 0 is g itself, signed zeros
 // included); partial sums of |clamp(d, max=0)| (NaN stays NaN).
 __global__ __launch_bounds__(kLossThreads) void neg_reg_kernel(
@@ -223,6 +248,29 @@ extern "C" int sphrt_wsq_residual_f64(const double* yhat, const void* y, int y_i
                            st, yhat, (const float*)y, n, ray_scale, weight, order, r_scaled,
                            partial_sums);
     return check_launch("wsq_residual");
+}
+
+extern "C" int sphrt_robust_residual_f64(const double* yhat, const void* y, int y_is_f64,
+                                         int64_t n, int kind, double delta,
+                                         const double* ray_scale, const double* weight,
+                                         const int32_t* order, double* r_scaled,
+                                         double* partial_sums, void* stream) {
+    double rd;
+    if (int e = refuse_robust(kind, delta, rd)) return e;
+    if (n <= 0) return fail("sphrt_robust_residual_f64: empty measurement");
+    if (!yhat || !y || !ray_scale || !weight || !r_scaled || !partial_sums)
+        return fail("null buffer");
+    StreamGuard guard(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (y_is_f64)
+        hipLaunchKernelGGL(robust_residual_kernel<double>, dim3(loss_grid(n)), dim3(kLossThreads),
+                           0, st, yhat, (const double*)y, n, rd, ray_scale, weight, order,
+                           r_scaled, partial_sums);
+    else
+        hipLaunchKernelGGL(robust_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads),
+                           0, st, yhat, (const float*)y, n, rd, ray_scale, weight, order, r_scaled,
+                           partial_sums);
+    return check_launch("robust_residual");
 }
 
 extern "C" int sphrt_neg_reg_f64(const double* d, int64_t n, double c_neg, double* g,

@@ -54,15 +54,21 @@ namespace sphrt {
 // for the one lane that streams a sorted list from the workspace.
 enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4,
        MODE_SCATTER = 5, MODE_NORMAL = 6, MODE_SCATTER_FIXED = 7, MODE_NORMAL_FIXED = 8,
-       MODE_NORMAL_W = 9, MODE_NORMAL_W_FIXED = 10 };
+       MODE_NORMAL_W = 9, MODE_NORMAL_W_FIXED = 10, MODE_NORMAL_R = 11, MODE_NORMAL_R_FIXED = 12 };
 constexpr bool mode_scatter(int m) { return m == MODE_SCATTER || m == MODE_SCATTER_FIXED; }
 // (the weighted normal modes: the residual's factor per ray and channel, TraceOut::ray_scale)
-constexpr bool mode_weighted(int m) { return m == MODE_NORMAL_W || m == MODE_NORMAL_W_FIXED; }
+// (the robust normal modes: the weighted ones with psi of the residual in the residual's place,
+// robust_psi; TraceOut::robust_delta picks psi)
+constexpr bool mode_robust(int m) { return m == MODE_NORMAL_R || m == MODE_NORMAL_R_FIXED; }
+constexpr bool mode_weighted(int m) {
+    return m == MODE_NORMAL_W || m == MODE_NORMAL_W_FIXED || mode_robust(m);
+}
 constexpr bool mode_normal(int m) {
     return m == MODE_NORMAL || m == MODE_NORMAL_FIXED || mode_weighted(m);
 }
 constexpr bool mode_fixed(int m) {
-    return m == MODE_SCATTER_FIXED || m == MODE_NORMAL_FIXED || m == MODE_NORMAL_W_FIXED;
+    return m == MODE_SCATTER_FIXED || m == MODE_NORMAL_FIXED || m == MODE_NORMAL_W_FIXED ||
+           m == MODE_NORMAL_R_FIXED;
 }
 constexpr int kNone = 0x7fffffff;  // "no update" in the forward-fill scans
 constexpr int kWavesPerBlock = 4;
@@ -436,7 +442,10 @@ struct TraceOut {
     int32_t* counts;          // COUNT
     const int64_t* row_ptr;   // FILL
     int32_t* vox;
-    double* len;
+    union {                   // one slot (FILL / EMIT and NORMAL_R* never meet): TraceOut keeps its
+        double* len;              // size, and the kernel arguments of the other modes their place
+        double robust_delta;      // NORMAL_R*: Huber's delta (> 0), or 0 for the sign (ABS)
+    };
     const T* density;         // INTEGRATE; SCATTER: y, its channels out_chan_stride apart
     int64_t n_chan, chan_stride, ray_chan_div;
     T* out;
@@ -531,6 +540,15 @@ __device__ __forceinline__ double residual_factor(const TraceOut<T>& o, int64_t 
     else return o.scale;
 }
 
+// NORMAL: what the scatter weighs a ray's lengths with, from the residual r = sum - m of the
+// per-ray element rc: r * factor (two roundings with r's), or (NORMAL_R*) psi(r) * ray_scale[rc]
+// (robust_psi, common.hpp; robust_delta is wave-uniform: one scalar branch).
+template <int MODE, typename T>
+__device__ __forceinline__ double residual_weight(const TraceOut<T>& o, int64_t rc, double r) {
+    if constexpr (mode_robust(MODE)) return robust_psi(r, o.robust_delta) * o.ray_scale[rc];
+    else return r * residual_factor<MODE>(o, rc);
+}
+
 // The segment sink: what every wave-level path does with a ray's list once it is compacted —
 // (seg_vox, seg_len), nseg of them in LDS, and the head segment (hlen in voxel hvox, when `head`).
 //   COUNT        the count.
@@ -542,7 +560,9 @@ __device__ __forceinline__ double residual_factor(const TraceOut<T>& o, int64_t 
 //                NORMAL): acc[c][vox] += w * len, one acc_add per segment, with w the ray's y
 //                (SCATTER) or the residual (sum - m) * scale (NORMAL; wave_sum leaves the sum in
 //                every lane; two roundings, sphrt_sq_residual_f64's; NORMAL_W*: scale is
-//                ray_scale[rc], one wave-uniform load per ray and channel, residual_factor).
+//                ray_scale[rc], one wave-uniform load per ray and channel, residual_factor;
+//                NORMAL_R*: psi(sum - m) * ray_scale[rc], psi once per ray and channel,
+//                residual_weight).
 template <int MODE, typename T>
 __device__ __forceinline__ void consume_list(const TraceOut<T>& o, int64_t ray, int lane, int nseg,
                                              const int32_t* seg_vox, const double* seg_len,
@@ -577,7 +597,7 @@ __device__ __forceinline__ void consume_list(const TraceOut<T>& o, int64_t ray, 
                 for (int q = lane; q < nseg; q += 64) sum += (double)rho[seg_vox[q]] * seg_len[q];
                 sum = wave_sum(sum);
                 if (lane == 0) o.out[rc] = (T)sum;
-                if constexpr (kScatter) w = (sum - o.meas[rc]) * residual_factor<MODE>(o, rc);
+                if constexpr (kScatter) w = residual_weight<MODE>(o, rc, sum - o.meas[rc]);
             } else {
                 w = (double)o.density[rc];
             }
@@ -1560,7 +1580,7 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
                     const int64_t rc = ray_index(o, c, ray);
                     double w;                                  // the residual, or y
                     if constexpr (mode_normal(MODE))
-                        w = ((double)o.out[rc] - o.meas[rc]) * residual_factor<MODE>(o, rc);
+                        w = residual_weight<MODE>(o, rc, (double)o.out[rc] - o.meas[rc]);
                     else
                         w = (double)o.density[rc];
                     acc_add<MODE>(o.acc, c * o.chan_stride + vx, w * len, fx);
@@ -2332,7 +2352,7 @@ static TraceOut<T> fused_out(const T* in, int64_t n_chan, int64_t chan_stride, i
                              T* out, int64_t ray_stride, void* acc = nullptr,
                              const double* m = nullptr, double scale = 0.0,
                              const void* scale_rec = nullptr,
-                             const double* ray_scale = nullptr) {
+                             const double* ray_scale = nullptr, double robust_delta = 0.0) {
     TraceOut<T> o{};
     o.density = in;
     o.n_chan = n_chan;
@@ -2345,6 +2365,7 @@ static TraceOut<T> fused_out(const T* in, int64_t n_chan, int64_t chan_stride, i
     if (ray_scale) o.ray_scale = ray_scale;
     else o.scale = scale;
     o.fixed_rec = static_cast<const int32_t*>(scale_rec);
+    if (robust_delta != 0.0) o.robust_delta = robust_delta;   // (shares len's slot: null here)
     return o;
 }
 static const char* refuse_channels(int64_t n_chan, int64_t ray_chan_div) {
@@ -2454,13 +2475,14 @@ static int run_backproject(const sphrt_plan* plan, const sphrt_rays* rays, const
                                              y_chan_stride, acc, nullptr, 0.0, scale_rec),
                            workspace, workspace_size, stream);
 }
-// (NORMAL_W*: the residual's factor is ray_scale, laid out as m, and `scale` is unused)
+// (NORMAL_W*, NORMAL_R*: the residual's factor is ray_scale, laid out as m, and `scale` is unused;
+// NORMAL_R*: robust_delta is TraceOut's, the entry's refusals of kind and delta made already)
 template <int MODE>
 static int run_normal(const sphrt_plan* plan, const sphrt_rays* rays, const double* density,
                       const double* m, double scale, const double* ray_scale, int64_t n_chan,
                       int64_t chan_stride, int64_t ray_chan_div, double* yhat,
                       int64_t y_chan_stride, void* acc, const void* scale_rec, void* workspace,
-                      size_t workspace_size, void* stream) {
+                      size_t workspace_size, void* stream, double robust_delta = 0.0) {
     if constexpr (mode_fixed(MODE)) {
         if (int e = refuse_fixed(plan, rays, n_chan, scale_rec)) return e;
     }
@@ -2472,7 +2494,8 @@ static int run_normal(const sphrt_plan* plan, const sphrt_rays* rays, const doub
         return e;
     return run_trace<MODE>(plan, rays, nullptr,
                            fused_out(density, n_chan, chan_stride, ray_chan_div, yhat,
-                                     y_chan_stride, acc, m, scale, scale_rec, ray_scale),
+                                     y_chan_stride, acc, m, scale, scale_rec, ray_scale,
+                                     robust_delta),
                            workspace, workspace_size, stream);
 }
 
@@ -2537,6 +2560,34 @@ extern "C" int sphrt_trace_normal_weighted_fixed_f64(
     return run_normal<MODE_NORMAL_W_FIXED>(plan, rays, density, m, 0.0, ray_scale, n_chan,
                                            chan_stride, ray_chan_div, yhat, y_chan_stride, acc,
                                            scale_rec, workspace, workspace_size, stream);
+}
+
+// The robust entries: refuse_robust (common.hpp) first — kind and delta, giving robust_delta —
+// then the weighted entries' path.
+extern "C" int sphrt_trace_normal_robust_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                             const double* density, const double* m,
+                                             const double* ray_scale, int kind, double delta,
+                                             int64_t n_chan, int64_t chan_stride,
+                                             int64_t ray_chan_div, double* yhat,
+                                             int64_t y_chan_stride, double* acc, void* workspace,
+                                             size_t workspace_size, void* stream) {
+    double rd;
+    if (int e = refuse_robust(kind, delta, rd)) return e;
+    return run_normal<MODE_NORMAL_R>(plan, rays, density, m, 0.0, ray_scale, n_chan, chan_stride,
+                                     ray_chan_div, yhat, y_chan_stride, acc, nullptr, workspace,
+                                     workspace_size, stream, rd);
+}
+
+extern "C" int sphrt_trace_normal_robust_fixed_f64(
+    const sphrt_plan* plan, const sphrt_rays* rays, const double* density, const double* m,
+    const double* ray_scale, int kind, double delta, int64_t n_chan, int64_t chan_stride,
+    int64_t ray_chan_div, double* yhat, int64_t y_chan_stride, int64_t* acc,
+    const void* scale_rec, void* workspace, size_t workspace_size, void* stream) {
+    double rd;
+    if (int e = refuse_robust(kind, delta, rd)) return e;
+    return run_normal<MODE_NORMAL_R_FIXED>(plan, rays, density, m, 0.0, ray_scale, n_chan,
+                                           chan_stride, ray_chan_div, yhat, y_chan_stride, acc,
+                                           scale_rec, workspace, workspace_size, stream, rd);
 }
 
 template <typename F>

@@ -155,6 +155,15 @@ class ShardedOperator:
         return self.n_obs * math.prod(self.view_shape)
 
 
+def _declined(loss_fns):
+    """Does gd() keep these terms out of its direct loop, whatever retrieval._direct_plan takes
+    on one GPU: a tensor projection_mask, or a robust fidelity term (AbsLoss, HuberLoss) — only
+    the unmasked SquareLoss loop is worked out over ranks."""
+    from .loss import AbsLoss, HuberLoss
+    return any(isinstance(fn.projection_mask, tr.Tensor) or type(fn) in (AbsLoss, HuberLoss)
+               for fn in loss_fns)
+
+
 def gd(f, y_local, model, coeffs=None, num_iterations=100, loss_fns=None, optim=tr.optim.Adam,
        progress_bar=False, device=None, **kwargs):
     """Data-parallel counterpart of retrieval.gd for a ShardedOperator (static grids).
@@ -180,11 +189,11 @@ def gd(f, y_local, model, coeffs=None, num_iterations=100, loss_fns=None, optim=
         coeffs = tr.ones(model.coeffs_shape, dtype=tr.float64, device=device or f.device)
     coeffs.requires_grad_()
     opt = optim([coeffs], **kwargs)
-    # (a tensor projection_mask, which the single-GPU direct loop takes, is declined here: the
-    # rank's share of a mask over the whole stack is not worked out — the autograd loop)
-    masked = any(isinstance(fn.projection_mask, tr.Tensor) for fn in loss_fns)
+    # (a tensor projection_mask and the robust terms, which the single-GPU direct loop takes, are
+    # declined here: the rank's share of them over the whole stack is not worked out — the
+    # autograd loop)
     plan = _direct_plan(f.local, y_local, model, coeffs, loss_fns, [coeffs]) \
-        if hasattr(f.local, '_csr') and not masked else None
+        if hasattr(f.local, '_csr') and not _declined(loss_fns) else None
     # the two loops issue different collectives: every rank takes the direct loop or none does
     flag = tr.tensor([1.0 if plan is not None else 0.0], dtype=tr.float64, device=coeffs.device)
     if f._host_staged(flag):

@@ -3,6 +3,8 @@
 A loss is built once, weighted by multiplying with a scalar (``5 * SquareLoss()``), and called
 by ``gd()`` as ``loss(f, y, density, coeffs)``; the fidelity losses call the Operator ``f``.
 """
+import numbers
+
 import torch as t
 
 
@@ -76,6 +78,30 @@ class AbsLoss(Loss):
 
     def compute(self, f, y, d, c):
         return t.mean(_scaled(self.projection_mask, (y - f(_scaled(self.volume_mask, d))).abs()))
+
+
+class HuberLoss(Loss):
+    """mean(huber(f(d) - y)): 0.5 r^2 where |r| < delta, delta (|r| - 0.5 delta) beyond —
+    quadratic near the solution (where AbsLoss's constant-magnitude gradient makes Adam
+    oscillate), linear in the outliers.  Not in the reference.  A float32 y against a float64
+    forward is promoted, as torch's arithmetic promotes it."""
+    kind = 'fidelity'
+
+    def __init__(self, delta=1.0, **kwargs):
+        # (a real number — int, float, a numpy scalar; no bool, no tensor — finite and > 0)
+        if isinstance(delta, bool) or not isinstance(delta, numbers.Real) or not delta > 0 \
+                or delta == float('inf'):
+            raise ValueError(f'HuberLoss needs a finite delta > 0, not {delta!r}')
+        self.delta = float(delta)
+        super().__init__(**kwargs)
+
+    def compute(self, f, y, d, c):
+        pred = f(_scaled(self.volume_mask, d))
+        if y.dtype != pred.dtype:     # (huber_loss itself refuses mixed dtypes)
+            dt = t.promote_types(y.dtype, pred.dtype)
+            y, pred = y.to(dt), pred.to(dt)
+        return t.mean(_scaled(self.projection_mask, t.nn.functional.huber_loss(
+            pred, y, reduction='none', delta=self.delta)))
 
 
 class CheaterLoss(Loss):

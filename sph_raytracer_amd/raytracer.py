@@ -19,6 +19,7 @@ Differences from the reference, by design:
 import ctypes
 import functools
 import math
+import numbers
 import os
 import weakref
 
@@ -1167,6 +1168,90 @@ def _fused_gradient(parts, grid, density, m, scale, dev, deterministic=False, we
             _from_f64(acc, rdt, dev).reshape(density.shape).to(rdev))
 
 
+ROBUST_KINDS = {'abs': 1, 'huber': 2}    # SPHRT_RESID_ABS, SPHRT_RESID_HUBER (include/sphrt.h)
+
+
+def _robust_args(loss, delta):
+    """-> None for loss='square', else (kind, delta) as the robust C entries take them (delta 0.0
+    for 'abs').  ValueError on an unknown loss (anything but those three strings), a 'huber'
+    without a finite delta > 0 and a delta given to anything else (host only).  delta is a real
+    number (`_real_delta`: a Python or numpy scalar; a tensor is refused, reading it could
+    sync)."""
+    if not isinstance(loss, str) or loss not in ('square', 'abs', 'huber'):
+        raise ValueError(f"loss must be 'square', 'abs' or 'huber', not {loss!r}")
+    if loss == 'huber':
+        if not _real_delta(delta):
+            raise ValueError(f"loss='huber' needs a finite delta > 0, not {delta!r}")
+        return ROBUST_KINDS['huber'], float(delta)
+    if delta is not None:
+        raise ValueError(f"delta belongs to loss='huber', not loss={loss!r}")
+    if loss == 'abs':
+        return ROBUST_KINDS['abs'], 0.0
+    return None
+
+
+def _real_delta(delta):
+    """Is `delta` a Huber delta: a real number (numbers.Real: int, float, numpy scalars; no
+    bool, no tensor), finite and > 0."""
+    return (isinstance(delta, numbers.Real) and not isinstance(delta, bool)
+            and math.isfinite(delta) and delta > 0)
+
+
+def _launch_normal_robust(parts, grid, d, m, rs, robust, n_chan, div, yhat, acc, dev, fixed=None,
+                          scaled=False):
+    """_launch_normal's robust form, sphrt_trace_normal_robust_f64 / _fixed_f64: the zeroed acc
+    gains A^T(rs psi(A d - m)) with robust = (kind, delta) (_robust_args) and rs the flat float64
+    factor per measurement on `dev`.  The fixed form's bound is max|rs| L (abs) or max|rs| delta L
+    (huber), taken on the device: nothing is read back.  It depends on rs alone, so a caller
+    whose rs does not change passes `scaled` once fixed[1] holds the record of an earlier call
+    (gd's loop: one reduction over the rays per loop, not per iteration)."""
+    plan, batch, ws = parts
+    kind, delta = robust
+    if rs.numel() != m.numel():
+        raise ValueError(f'{rs.numel()} ray factors for {m.numel()} measurements')
+    lib, stream = _lib.load(), _lib.stream_of(dev)
+    if fixed is not None:
+        L = _outer_diameter(grid)
+        fa = delta * L if kind == ROBUST_KINDS['huber'] else L
+        if not scaled:
+            _lib.check(lib.sphrt_fixed_scale_f64(_lib.ptr(rs), rs.numel(), fa, None, 0, 0.0,
+                                                 _lib.ptr(fixed[1]), stream),
+                       'sphrt_fixed_scale_f64')
+        _lib.check(lib.sphrt_trace_normal_robust_fixed_f64(
+            plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), _lib.ptr(rs), kind, delta, n_chan,
+            math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(fixed[0]),
+            _lib.ptr(fixed[1]), _lib.ptr(ws), ws.numel(), stream),
+            'sphrt_trace_normal_robust_fixed_f64')
+        _fixed_finalize(fixed, acc, dev)
+        return
+    _lib.check(lib.sphrt_trace_normal_robust_f64(
+        plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), _lib.ptr(rs), kind, delta, n_chan,
+        math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(acc), _lib.ptr(ws),
+        ws.numel(), stream), 'sphrt_trace_normal_robust_f64')
+
+
+def _fused_robust_gradient(parts, grid, density, m, scale, dev, robust, deterministic=False,
+                           weights=None):
+    """_fused_gradient for a robust loss: (A density, A^T(ray_scale psi(A density - m))) from one
+    trace, ray_scale = weights * scale per measurement (_ray_scale), or `scale` expanded once."""
+    n_chan, div, out_shape = _gradient_layout(grid, parts[1].shape, density.shape, m.shape)
+    d, mv = _to_f64(density, dev), _to_f64(m, dev)
+    if weights is None:
+        rs = tr.full((mv.numel(),), float(scale), dtype=tr.float64, device=dev)
+    else:
+        rs, _ = _ray_scale(weights, scale, m.shape, dev, False)
+    yhat = tr.empty(mv.numel(), dtype=tr.float64, device=dev)
+    if deterministic:
+        acc = tr.empty(d.numel(), dtype=tr.float64, device=dev)
+        fixed = _fixed_buffers(d.numel(), dev)
+    else:
+        acc, fixed = tr.zeros(d.numel(), dtype=tr.float64, device=dev), None
+    _launch_normal_robust(parts, grid, d, mv, rs, robust, n_chan, div, yhat, acc, dev, fixed)
+    rdt, rdev = density.dtype, density.device
+    return (_from_f64(yhat, rdt, dev).reshape(out_shape).to(rdev),
+            _from_f64(acc, rdt, dev).reshape(density.shape).to(rdev))
+
+
 def _time_slices_rule(grid, time_slices):
     """Operator.T's rule: a dynamic grid back-projects only on request (raytracer.py:733-734)."""
     if grid.dynamic and not time_slices:
@@ -2190,7 +2275,9 @@ class MatrixFreeOperator:
     ``op.residual_gradient(density, m, scale)`` gives ``op(density)`` and
     ``op.T(scale * (op(density) - m))`` from one trace instead of two; with ``weights=w`` (a
     mask, noise weights) ``op.T(w * scale * (op(density) - m))``, still from one trace, and gd()
-    over a ``SquareLoss(projection_mask=w)`` runs its direct loop on that call.  There are
+    over a ``SquareLoss(projection_mask=w)`` runs its direct loop on that call; with
+    ``loss='abs'`` or ``loss='huber', delta=d`` the residual is replaced by its sign or its clamp
+    to +-d (gd() over an ``AbsLoss`` or a ``HuberLoss``).  There are
     no ``regs`` / ``lens`` / ``segments`` views: nothing is stored to show.  The workspace is
     shared by the calls: use an operator from one stream at a time."""
 
@@ -2246,7 +2333,8 @@ class MatrixFreeOperator:
         _, _, dshape = _adjoint_layout(self.grid, self._ray_shape, y.shape)
         return self._apply_adjoint(y, dshape, y.dtype, self._rdev)
 
-    def residual_gradient(self, density, measurements, scale=1.0, weights=None):
+    def residual_gradient(self, density, measurements, scale=1.0, weights=None, loss='square',
+                          delta=None):
         """-> (yhat, grad) from one trace (sphrt_trace_normal_f64): ``yhat = op(density)`` and
         ``grad = A^T(scale * (yhat - measurements))``, the gradient in ``density`` of
         ``0.5 * scale * ((op(density) - measurements) ** 2).sum()`` — what ``op`` followed by
@@ -2263,6 +2351,17 @@ class MatrixFreeOperator:
         readback per call, a host sync (the atomic mode reads nothing back), and a weight that is
         not finite raises ValueError.  ``weights=None`` is the unweighted call, unchanged.
 
+        ``loss`` makes the fidelity robust to outliers nobody marked: ``'abs'`` (L1) and
+        ``'huber'`` (with ``delta`` > 0, required for it and refused otherwise) give
+        ``grad = A^T(ray_scale * psi(yhat - measurements))`` with psi the sign of the residual
+        (-1, 0, +1: an exact zero residual contributes nothing) or the residual clamped to
+        [-delta, delta], and ``ray_scale = weights.to(float64) * scale`` (``scale`` alone without
+        weights) — the gradient of ``scale * (weights * |r|).sum()`` and of ``scale * (weights *
+        huber(r, delta)).sum()``, still from one trace (sphrt_trace_normal_robust_f64).  psi is
+        bounded, so the deterministic form bounds its terms on the device and reads nothing back;
+        a factor that is not finite then gives NaN everywhere.  ``loss='square'`` is the call
+        above, unchanged.
+
         ``measurements`` has ``op(density)``'s shape.  Static grids take leading channel axes; a
         dynamic grid pairs time slices with views as the forward does, so ``grad`` is autograd's
         gradient of the dynamic forward.  Computed in float64 (``yhat`` is bitwise the float64
@@ -2272,6 +2371,7 @@ class MatrixFreeOperator:
         device.  Not differentiable."""
         density, m = tr.as_tensor(density), tr.as_tensor(measurements)
         _gradient_layout(self.grid, self._ray_shape, density.shape, m.shape)   # (host only)
+        robust = _robust_args(loss, delta)                                      # (host only)
         if weights is not None:
             weights = tr.as_tensor(weights)
             if weights.dtype not in (tr.bool, tr.float32, tr.float64):
@@ -2284,6 +2384,10 @@ class MatrixFreeOperator:
                 raise ValueError(f'weights of shape {tuple(weights.shape)} do not broadcast to '
                                  f'the measurements {tuple(m.shape)}')
         with tr.cuda.device(self._cdev):
+            if robust is not None:
+                return _fused_robust_gradient(self._parts, self.grid, density, m, scale,
+                                              self._cdev, robust, bool(self.deterministic),
+                                              weights)
             return _fused_gradient(self._parts, self.grid, density, m, scale, self._cdev,
                                    bool(self.deterministic), weights)
 
@@ -2310,6 +2414,21 @@ class MatrixFreeOperator:
             fixed = None
         _launch_normal(self._parts, self.grid, d, m, scale, 1, 0, yhat, acc, self._cdev, fixed,
                        weighted)
+
+    def _robust_into(self, d, m, rs, robust, yhat, acc, fixed=None, scaled=False):
+        """_normal_into for a robust loss: `rs` the flat float64 factor per measurement,
+        `robust` = (kind, delta) (_robust_args); the zeroed acc gains A^T(rs psi(A d - m)).
+        `scaled`: the caller's `fixed` already holds the scale record of this rs and robust
+        (an earlier call wrote it), so it is not formed again."""
+        if self.deterministic:
+            if fixed is None:
+                fixed, scaled = self._fixed_buffers(), False
+            else:
+                fixed[0].zero_()
+        else:
+            fixed = None
+        _launch_normal_robust(self._parts, self.grid, d, m, rs, robust, 1, 0, yhat, acc,
+                              self._cdev, fixed, scaled)
 
     def __repr__(self):
         if self.dynamic:

@@ -10,7 +10,7 @@ import math
 
 import torch as t
 
-from .loss import NegRegularizer, SquareLoss
+from .loss import AbsLoss, HuberLoss, NegRegularizer, SquareLoss
 from .model import FullyDenseModel
 
 try:
@@ -125,9 +125,10 @@ def _unit(m):
 def _direct_plan(f, y, model, coeffs, loss_fns, optim_vars):
     """The loss terms of a loop `_gd_direct` runs without autograd, or None.  It covers the
     examples/static_retrieval.py loop: a FullyDenseModel (the coefficients are the density) on a
-    static Operator, one SquareLoss and at most one NegRegularizer, scalar weights, no masks but
-    the SquareLoss's projection_mask (`_ray_mask`: per-ray weights, a mask of bad pixels), the
-    coefficients the only optimised variable.  Anything else takes the autograd loop."""
+    static Operator, one fidelity term — a SquareLoss, an AbsLoss or a HuberLoss, exactly those
+    types — and at most one NegRegularizer, scalar weights, no masks but the fidelity term's
+    projection_mask (`_ray_mask`: per-ray weights, a mask of bad pixels), the coefficients the
+    only optimised variable.  Anything else takes the autograd loop."""
     from .raytracer import Operator
     if not isinstance(f, Operator) or f.dynamic or f._csr is None or y is None:
         return None
@@ -147,7 +148,7 @@ def _fused_plan(f, y, model, coeffs, loss_fns, optim_vars):
 
 
 def _ray_mask(mask, y):
-    """Is `mask` a SquareLoss projection_mask `_gd_direct` weighs the residual with: a constant
+    """Is `mask` a fidelity term's projection_mask `_gd_direct` weighs the residual with: a constant
     tensor on y's device, bool, float32 or float64, broadcastable to y's shape."""
     if not (isinstance(mask, t.Tensor) and mask.device == y.device and not mask.requires_grad
             and mask.dtype in (t.bool, t.float32, t.float64)):
@@ -158,9 +159,24 @@ def _ray_mask(mask, y):
         return False
 
 
+_FIDELITY = (SquareLoss, AbsLoss, HuberLoss)    # the direct loops' fidelity terms, by exact type
+
+
+def _robust_of(fid):
+    """(kind, delta) of a robust fidelity term as the C entries take them, None for SquareLoss."""
+    from .raytracer import ROBUST_KINDS
+    if type(fid) is AbsLoss:
+        return ROBUST_KINDS['abs'], 0.0
+    if type(fid) is HuberLoss:
+        return ROBUST_KINDS['huber'], float(fid.delta)
+    return None
+
+
 def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
-    """(SquareLoss, NegRegularizer or None) when model, variables, measurements and loss terms
-    are those `_gd_direct` runs over the operator `f`, else None."""
+    """(fidelity term, NegRegularizer or None) when model, variables, measurements and loss terms
+    are those `_gd_direct` runs over the operator `f`, else None.  The fidelity term is exactly
+    one SquareLoss, AbsLoss or HuberLoss (`_FIDELITY`; a subclass may compute anything: the
+    autograd loop)."""
     if type(model) is not FullyDenseModel or hasattr(model, 'proj'):
         return None
     if len(optim_vars) != 1 or optim_vars[0] is not coeffs or coeffs.dtype != t.float64:
@@ -177,9 +193,9 @@ def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
                 and _unit(fn.volume_mask)):
             return None
         if not (_unit(fn.projection_mask)
-                or type(fn) is SquareLoss and _ray_mask(fn.projection_mask, y)):
+                or type(fn) in _FIDELITY and _ray_mask(fn.projection_mask, y)):
             return None
-        if type(fn) is SquareLoss and sq is None:
+        if type(fn) in _FIDELITY and sq is None:
             sq = fn
         elif type(fn) is NegRegularizer and neg is None:
             neg = fn
@@ -211,6 +227,14 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     multiplies by 2 * (y - f(d)) (exact), so the adjoint's input is (f(d) - y) * s with
     s = ((lam / N) * w) * 2, formed once before the loop; the loss sums w * (r * r)
     (sphrt_wsq_residual_f64; fused: sphrt_trace_normal_weighted_f64 with ray_scale = s).
+    AbsLoss, lam * mean(w * |y - f(d)|), and HuberLoss, lam * mean(w * huber(f(d), y)): the mean
+    and the mask give s = (lam / N) * w_i as above (one rounding, none for a unit mask); abs's
+    backward multiplies by sign(y - f(d)) and the subtraction negates — s * sign(f(d) - y), exact —
+    and huber_loss's backward gives -(s * delta), s * delta or (f(d) - y) * s by the residual's
+    side of +-delta, which is s * clamp(f(d) - y, -delta, delta) (one rounding either way).  So
+    the adjoint's input is s * psi(f(d) - y) (sphrt_robust_residual_f64, which also sums
+    w * |r| or w * huber(r); fused: sphrt_trace_normal_robust_f64 with ray_scale = s).  A NaN
+    residual has a zero gradient under AbsLoss and a NaN one under HuberLoss, as in torch.
     Gradient of lam * mean(|clip(d, max=0)|): -(lam / N) where d < 0, else 0 (sign(0) = 0).
     The two are summed (IEEE addition commutes, so the order autograd accumulates them in does
     not matter) and handed to the optimiser as coeffs.grad.
@@ -263,7 +287,19 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     # a projection_mask: the loss's weights w and the residual's factors s, once, laid out as the
     # residual kernel reads y (in trace order where y was permuted above)
     w_res = s_res = weighted = None
-    if isinstance(sq.projection_mask, t.Tensor):
+    robust = _robust_of(sq)
+    if robust is not None:
+        # a robust term's factors are always arrays (a unit mask: ones, and lam / N itself)
+        if isinstance(sq.projection_mask, t.Tensor):
+            w_res = sq.projection_mask.detach().to(t.float64).expand(yd.shape).contiguous() \
+                .reshape(-1)
+            s_res = c_sq * w_res
+        else:
+            w_res = t.ones(n_meas, dtype=t.float64, device=coeffs.device)
+            s_res = t.full((n_meas,), c_sq, dtype=t.float64, device=coeffs.device)
+        if keep_rows is not None:
+            w_res, s_res = (v.index_select(0, f._ray_id_long()) for v in (w_res, s_res))
+    elif isinstance(sq.projection_mask, t.Tensor):
         w_res = sq.projection_mask.detach().to(t.float64).expand(yd.shape).contiguous().reshape(-1)
         s_res = (c_sq * w_res) * 2
         if keep_rows is not None:
@@ -302,7 +338,13 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                     # f(d) into yhat_buf and A^T((f(d) - y) * (2 lam / N)) into a zeroed g from
                     # one trace; the residual launch below then only sums the loss
                     g = t.zeros_like(d)
-                    if weighted is None:
+                    if robust is not None:
+                        # (a robust term: A^T(s psi(f(d) - y)), the fixed-point bound formed on
+                        # the device from s)
+                        # (s does not change: the record is written by the first iteration)
+                        f._robust_into(d, m64, s_res, robust, yhat_buf, g, *fixed,
+                                       scaled=bool(fixed) and it > 0)
+                    elif weighted is None:
                         f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed)
                     else:
                         f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed, weighted=weighted)
@@ -323,7 +365,14 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 # r * r (the loss) in one launch (csrc/loss.hip)
                 # (in the trace's ray order when the adjoint takes that: no permutation launch)
                 r_scaled = t.empty_like(yhat)
-                if w_res is None:
+                if robust is not None:
+                    # (r_scaled = psi(r) * s_i, and the partial sums of w_i * |r| or w_i * huber(r))
+                    _lib.check(lib.sphrt_robust_residual_f64(
+                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
+                        robust[0], robust[1], _lib.ptr(s_res), _lib.ptr(w_res),
+                        _lib.ptr(res_order), _lib.ptr(r_scaled), _lib.ptr(part_sq[it]), stream),
+                        'sphrt_robust_residual_f64')
+                elif w_res is None:
                     _lib.check(lib.sphrt_sq_residual_f64(
                         _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
                         2 * c_sq, _lib.ptr(res_order), _lib.ptr(r_scaled), _lib.ptr(part_sq[it]),

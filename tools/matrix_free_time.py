@@ -9,6 +9,8 @@ trace + scatter) beside the stored-trace Operator, on one GPU.
                                      [--out profiles/matrix_free_deterministic_times.json]
     python tools/matrix_free_time.py --weighted [--configs c3] [--gd-config c5] [--base DIR]
                                      [--out profiles/matrix_free_weighted_times.json]
+    python tools/matrix_free_time.py --robust [--configs c3] [--gd-config c5] [--base DIR]
+                                     [--gd-only] [--out profiles/matrix_free_robust_times.json]
 
 Per config (bench.py's CONFIGS) two legs, each in a fresh child process with its own time limit
 (a leg that fails or runs out of time ends the run: nothing more is started):
@@ -54,6 +56,26 @@ processes and limits):
                SquareLoss(projection_mask=a 0/1 mask) + NegRegularizer, over a stored Operator
                and over a MatrixFreeOperator, through the direct loop and through the autograd
                loop (the plan functions made to return None), REPEATS times each.
+
+--robust measures the robust fidelity terms (one leg per config beside this tree's own weighted
+leg, then one gd leg; the same child processes and limits):
+  robust       float64, in one process, interleaved rounds: ms per
+               op.residual_gradient(x, m, s, weights=w, loss='abs') and loss='huber' with
+               op.deterministic False and True, and per two-call path each replaces, op(x) then
+               op.T(w * s * psi(op(x) - m)), in both modes.
+               With --base DIR (a checkout of the parent commit with its library built), that
+               tree's own --leg weighted runs in child processes before and after: the weighted
+               and the unweighted call there, the same box and session.  Derived: each robust
+               call against the parent's weighted call in the same mode and the parent's own
+               run-to-run spread; this tree's weighted and unweighted calls against the
+               parent's likewise (the segment sink they share was edited); each robust call
+               against its two calls;
+  gd_robust    ms per iteration of gd(..., 100) on bench.py's C5 retrieval problem with an
+               AbsLoss and with a HuberLoss (+ NegRegularizer), over a stored Operator and over a
+               MatrixFreeOperator (float64 atomics, and deterministic=True), through the direct
+               loop and through the autograd loop (the plan functions made to return None),
+               REPEATS times each.  --gd-only re-measures this leg alone and keeps the other
+               records of the output file.
 """
 import argparse
 import json
@@ -280,6 +302,200 @@ def derive_weighted(g, parent):
         d[f'gain_ms_{tag}'], d[f'spread_ms_{tag}'] = gain, spread
         d[f'faster_by_more_than_spread_{tag}'] = bool(gain > spread)
     return d
+
+
+HUBER_DELTA = 0.25      # (the --robust legs: with m, A x in [0, ~1) both branches are taken)
+
+
+def leg_robust(config, reps):
+    import torch
+    from sph_raytracer_amd import MatrixFreeOperator
+    grid, geom, dev, xs, ys = _problem(config)
+    ts = dict(time_slices=True) if grid.dynamic else {}
+    x, m = xs[torch.float64], ys[torch.float64]
+    g = torch.Generator(device=dev).manual_seed(1)
+    w = torch.rand(m.shape, dtype=torch.float64, device=dev, generator=g)
+    w[torch.rand(m.shape, device=dev, generator=g) < 0.2] = 0      # a fifth of the rays masked
+    op = MatrixFreeOperator(grid, geom, dynamic=grid.dynamic, device=dev)
+    r0 = op(x) - m
+    rec = {'config': config, 'rays': int(op._parts[1].n), 'reps': reps, 'repeats': REPEATS,
+           'dtype': 'float64', 'masked_fraction': float((w == 0).double().mean()),
+           'huber_delta': HUBER_DELTA,
+           'huber_inner_fraction': float((r0.abs() < HUBER_DELTA).double().mean())}
+    losses = {'abs': (dict(loss='abs'), torch.sign),
+              'huber': (dict(loss='huber', delta=HUBER_DELTA),
+                        lambda r: torch.clamp(r, -HUBER_DELTA, HUBER_DELTA))}
+
+    def mode(det, fn):
+        def run():
+            op.deterministic = det
+            return fn()
+        return run
+
+    def fused(kw):
+        return lambda: op.residual_gradient(x, m, 0.5, weights=w, **kw)
+
+    def two_calls(psi):
+        def run():
+            ax = op(x)
+            return ax, op.T((w * 0.5) * psi(ax - m), **ts)
+        return run
+
+    legs = []
+    for det, tag in ((False, 'atomic'), (True, 'deterministic')):
+        for loss, (kw, psi) in losses.items():
+            legs += [(f'{loss}_fused_ms_{tag}', mode(det, fused(kw))),
+                     (f'{loss}_two_calls_ms_{tag}', mode(det, two_calls(psi)))]
+    for name, fn in legs:
+        fn()                                                     # warm-up
+        rec[name] = []
+    for _ in range(REPEATS):                                   # interleaved: one of each per round
+        for name, fn in legs:
+            rec[name].append(events_ms(fn, reps))
+    return rec
+
+
+def derive_robust(g, own_weighted, parent):
+    """`parent`: the parent tree's weighted-leg records (before and after), `own_weighted`: this
+    tree's.  Every comparison with the parent: the medians, the parent's own spread (max - min
+    over all its repeats) and whether the excess over the parent stays within it."""
+    d = {}
+
+    def against_parent(name, mine, key):
+        p = [v for rec in parent for v in rec[key]]
+        d[name] = {'ms': _median(mine), 'parent_ms': _median(p), 'parent_key': key,
+                   'parent_spread_ms': max(p) - min(p),
+                   'minus_parent_ms': _median(mine) - _median(p),
+                   'no_slower_beyond_parent_spread':
+                       bool(_median(mine) - _median(p) <= max(p) - min(p))}
+
+    for tag in ('atomic', 'deterministic'):
+        for loss in ('abs', 'huber'):
+            f, t = g[f'{loss}_fused_ms_{tag}'], g[f'{loss}_two_calls_ms_{tag}']
+            spread = max(max(f) - min(f), max(t) - min(t))
+            gain = _median(t) - _median(f)
+            d[f'{loss}_{tag}'] = {'fused_ms': _median(f), 'two_calls_ms': _median(t),
+                                  'gain_ms': gain, 'spread_ms': spread,
+                                  'faster_by_more_than_spread': bool(gain > spread)}
+            if parent:
+                against_parent(f'{loss}_{tag}_against_parent_weighted', f,
+                               f'weighted_fused_ms_{tag}')
+        if parent:
+            against_parent(f'weighted_{tag}_against_parent',
+                           own_weighted[f'weighted_fused_ms_{tag}'], f'weighted_fused_ms_{tag}')
+    if parent:
+        against_parent('unweighted_against_parent', own_weighted['unweighted_fused_ms'],
+                       'unweighted_fused_ms')
+    return d
+
+
+def leg_gd_robust(config, iterations=100):
+    import torch
+    import bench
+    from sph_raytracer_amd import MatrixFreeOperator, Operator, retrieval
+    from sph_raytracer_amd.loss import AbsLoss, HuberLoss, NegRegularizer
+    from sph_raytracer_amd.model import FullyDenseModel
+    grid, geom = bench.build_geometry(bench.CONFIGS[config], 0, 1)
+    dev = torch.device('cuda', 0)
+    truth = torch.zeros(tuple(grid.shape), dtype=torch.float64, device=dev)
+    truth[:, 32:, :32] = 1                       # bench.py's C5 retrieval problem
+    truth[:, :32, 32:] = 1
+    model = FullyDenseModel(grid)
+    ops = {'stored': Operator(grid, geom, device=dev),
+           'matrix_free': MatrixFreeOperator(grid, geom, device=dev),
+           'matrix_free_deterministic': MatrixFreeOperator(grid, geom, device=dev,
+                                                           deterministic=True)}
+    y = ops['stored'](truth)
+    plans = retrieval._direct_plan, retrieval._fused_plan
+    terms = {'abs': AbsLoss, 'huber': lambda: HuberLoss(delta=HUBER_DELTA)}
+
+    def none(*a, **k):
+        return None
+
+    rec = {'config': config, 'iterations': iterations, 'repeats': REPEATS,
+           'huber_delta': HUBER_DELTA}
+    for loss, make in terms.items():
+        for kind, op in ops.items():
+            direct, auto, final = [], [], {}
+            for rnd in range(REPEATS + 1):                     # (round 0 warms up, untimed)
+                for name, into, (dp, fp) in (('direct', direct, plans),
+                                             ('autograd', auto, (none, none))):
+                    retrieval._direct_plan, retrieval._fused_plan = dp, fp
+                    try:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        _, _, losses = retrieval.gd(
+                            op, y.clone(), model, num_iterations=iterations if rnd else 3,
+                            lr=1e-1, loss_fns=[make(), NegRegularizer()], progress_bar=False)
+                        torch.cuda.synchronize()
+                        dt = time.perf_counter() - t0
+                    finally:
+                        retrieval._direct_plan, retrieval._fused_plan = plans
+                    if rnd:
+                        into.append(dt * 1e3 / iterations)
+                        final[name] = [v[-1] for v in losses.values()]
+            rec[f'{loss}_{kind}_direct_ms_per_iteration'] = direct
+            rec[f'{loss}_{kind}_autograd_ms_per_iteration'] = auto
+            rec[f'{loss}_{kind}_final_losses_direct'] = final['direct']
+            rec[f'{loss}_{kind}_final_losses_autograd'] = final['autograd']
+    return rec
+
+
+def derive_gd_robust(g):
+    d = {}
+    for loss in ('abs', 'huber'):
+        for kind in ('stored', 'matrix_free', 'matrix_free_deterministic'):
+            f = g[f'{loss}_{kind}_direct_ms_per_iteration']
+            a = g[f'{loss}_{kind}_autograd_ms_per_iteration']
+            spread = max(max(f) - min(f), max(a) - min(a))
+            gain = _median(a) - _median(f)
+            d[f'{loss}_{kind}'] = {'direct_ms_per_iteration': _median(f),
+                                   'autograd_ms_per_iteration': _median(a), 'gain_ms': gain,
+                                   'spread_ms': spread,
+                                   'faster_by_more_than_spread': bool(gain > spread)}
+    return d
+
+
+def main_robust(args):
+    out = {}
+
+    def save():
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            json.dump(out, fh, indent=1)
+            fh.write('\n')
+
+    base_tool = os.path.join(os.path.abspath(args.base), 'tools', os.path.basename(__file__)) \
+        if args.base else None
+    if args.gd_only:
+        with open(args.out) as fh:
+            out.update(json.load(fh))
+    for config in () if args.gd_only else args.configs:
+        parent = []
+        if base_tool:
+            before = _child('weighted', config, args.reps, base_tool)
+            if before is None:
+                return 1
+            parent.append(before)
+        own = _child('weighted', config, args.reps)
+        rec = _child('robust', config, args.reps) if own is not None else None
+        if rec is None:
+            return 1
+        if base_tool:
+            again = _child('weighted', config, args.reps, base_tool)
+            if again is None:
+                return 1
+            parent.append(again)
+        out[config] = {'robust': rec, 'weighted': own, 'parent_weighted': parent,
+                       'derived': derive_robust(rec, own, parent)}
+        save()
+    rec = _child('gd_robust', args.gd_config, None)
+    if rec is None:
+        return 1
+    out[f'gd_{args.gd_config}'] = {'gd_robust': rec, 'derived': derive_gd_robust(rec)}
+    save()
+    print(json.dumps({c: out[c]['derived'] for c in out}))
+    return 0
 
 
 def leg_gd_masked(config, iterations=100):
@@ -542,29 +758,37 @@ def main():
                     help='measure the fixed-point adjoint beside the float64-atomic one instead')
     ap.add_argument('--weighted', action='store_true',
                     help='measure the weighted gradient and gd with a projection mask instead')
+    ap.add_argument('--robust', action='store_true',
+                    help='measure the robust (abs, huber) gradient and gd with those terms instead')
+    ap.add_argument('--gd-only', action='store_true',
+                    help='--robust: the gd leg alone, into the existing output file')
     ap.add_argument('--base', default=None,
-                    help='--weighted: a checkout of the parent commit, its library built')
+                    help='--weighted, --robust: a checkout of the parent commit, its library built')
     ap.add_argument('--gd-config', default='c5',
-                    help='the gd leg\'s problem (--gradient, --weighted)')
+                    help='the gd leg\'s problem (--gradient, --weighted, --robust)')
     ap.add_argument('--leg', choices=('matrix_free', 'operator', 'gradient', 'gd', 'deterministic',
-                                      'weighted', 'gd_masked'),
+                                      'weighted', 'gd_masked', 'robust', 'gd_robust'),
                     help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'matrix_free_weighted_times.json'
+        args.out = os.path.join(ROOT, 'profiles', 'matrix_free_robust_times.json'
+                                if args.robust else 'matrix_free_weighted_times.json'
                                 if args.weighted else 'matrix_free_deterministic_times.json'
                                 if args.deterministic else 'matrix_free_gradient_times.json'
                                 if args.gradient else 'matrix_free_times.json')
-    if args.leg in ('gd', 'gd_masked'):
-        print(json.dumps((leg_gd if args.leg == 'gd' else leg_gd_masked)(args.configs[0])))
+    if args.leg in ('gd', 'gd_masked', 'gd_robust'):
+        fn = {'gd': leg_gd, 'gd_masked': leg_gd_masked, 'gd_robust': leg_gd_robust}[args.leg]
+        print(json.dumps(fn(args.configs[0])))
         return 0
     if args.leg:
         reps = args.reps or (5 if args.configs[0] == 'c3' else 20)
         fn = {'matrix_free': leg_matrix_free, 'operator': leg_operator,
               'gradient': leg_gradient, 'deterministic': leg_deterministic,
-              'weighted': leg_weighted}[args.leg]
+              'weighted': leg_weighted, 'robust': leg_robust}[args.leg]
         print(json.dumps(fn(args.configs[0], reps)))
         return 0
+    if args.robust:
+        return main_robust(args)
     if args.weighted:
         return main_weighted(args)
     if args.deterministic:
