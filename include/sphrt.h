@@ -523,6 +523,32 @@ int sphrt_robust_residual_f64(const double *yhat, const void *y, int y_is_f64, i
                               double *r_scaled, double *partial_sums, void *stream);
 int sphrt_neg_reg_f64(const double *d, int64_t n, double c_neg, double *g, double *partial_sums,
                       void *stream);
+/* SmoothRegularizer (loss.py; not in the reference): a difference penalty over the trailing axes
+ * (t, r, e, a) of a contiguous float64 density of n_batch * nt * nr * ne * na = n voxels,
+ *   P(d) = (1/N) * sum_ax w_ax * sum_{edges i -> i+1 along ax} rho(d[i+1] - d[i]),
+ * rho(r) = r^2 (kind 0), |r| (SPHRT_RESID_ABS) or torch's huber_loss (SPHRT_RESID_HUBER, delta).
+ * With wrap_a the edge from a = na - 1 to a = 0 closes every azimuth ring (na = 2: the pair is
+ * joined by two edges).  An axis of length 1 or of weight 0 has no edges and is not read; no edge
+ * crosses the batch axes (nt = 1: no time axis).  One launch writes
+ *   g_out[i] = h_i, or g_in[i] + h_i when g_in is given
+ *   G_i = (S_i * inv_n) * lam                                two roundings, in that order
+ *   S_i = sum over the present neighbours, in the order t-, t+, r-, r+, e-, e+, a-, a+, of
+ *         w_ax * rho'(d_i - d_nb),  rho' = 2r, sign(r) or clamp(r, +-delta)
+ *   h_i = G_i, or with part_neg set G_i - c_neg where d_i < 0 (sphrt_neg_reg_f64's term, so that
+ *         g_out = g_in + (G + neg): the order autograd leaves for [fidelity, two regularisers])
+ * and the workgroup partial sums (sphrt_loss_partials(n) each, fixed partition and order) of
+ * w_ax * rho(d[i+1] - d[i]) — every edge once, by its lower voxel; the wrap edge by the ring's
+ * last voxel — into part_smooth, and with part_neg those of |clamp(d, max=0)|, as
+ * sphrt_neg_reg_f64 leaves them.  The penalty is sum(part_smooth) * inv_n.  g_in may be NULL and
+ * may be g_out; NaN and inf are not special-cased (they propagate as in the torch formula).
+ * Fails on the host, before any launch, on an axis length < 1, n_batch < 1 (an empty volume),
+ * n >= 2^31, a weight that is not finite and >= 0, a non-finite inv_n or lam, an unknown kind or
+ * a HUBER delta that is not finite and > 0, a null part_smooth, g_out or d, and d == g_out. */
+int sphrt_smooth_reg_f64(const double *d, int64_t n_batch, int nt, int nr, int ne, int na,
+                         double wt, double wr, double we, double wa, int kind, double delta,
+                         int wrap_a, double inv_n, double lam, double c_neg,
+                         const double *g_in, double *g_out,
+                         double *part_smooth, double *part_neg, void *stream);
 /* One Adam step on float64 coefficients (torch.optim.Adam(fused=True), amsgrad and maximize off:
  * torch._fused_adam_'s per-element arithmetic, bitwise), step = the step count after this step's
  * increment (1, 2, ...).  With partial_sums set, the NegRegularizer is folded in first, as

@@ -131,6 +131,9 @@ _SIGNATURES = [
     ('sphrt_robust_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_vp, c_vp, c_vp,
                                           c_vp, c_vp, c_vp]),
     ('sphrt_neg_reg_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_vp, c_vp]),
+    ('sphrt_smooth_reg_f64', c_int, [c_vp, c_i64, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl,
+                                     c_dbl, c_int, c_dbl, c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp]),
     ('sphrt_adam_neg_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl,
                                    c_dbl, c_dbl, c_vp, ctypes.POINTER(CSR), c_vp]),
     ('sphrt_adam_foreach_neg_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl,

@@ -116,6 +116,99 @@ __global__ __launch_bounds__(kLossThreads) void neg_reg_kernel(
     block_partial(acc, part);
 }
 
+// SmoothRegularizer (loss.py): the difference penalty over the axes (t, r, e, a) of a density,
+//   P(d) = (1/N) sum_ax w_ax sum_{edges i -> i+1 along ax} rho(d[i+1] - d[i]),
+// rho = r^2 (kind 0), |r| (SPHRT_RESID_ABS) or torch's huber_loss (SPHRT_RESID_HUBER); with `wrap`
+// the azimuth ring closes: one more edge from a = na - 1 to a = 0 (na = 2: two edges between the
+// pair).  An axis of length 1 or of weight 0 has no edges (and is not read: no 0 * inf).
+struct SmoothDesc {
+    uint32_t nt, nr, ne, na;    // axis lengths (every axis before t is batch: no edges across it)
+    double wt, wr, we, wa;
+    int kind;                   // 0, SPHRT_RESID_ABS, SPHRT_RESID_HUBER
+    double delta;               // robust_psi's: > 0 for HUBER, 0 for ABS
+    int wrap;                   // the azimuth ring is closed (and na > 1)
+};
+
+// rho'(r): 2r, sign(r) or r clamped to +-delta.
+__device__ __forceinline__ double smooth_psi(double r, int kind, double delta) {
+    return kind == 0 ? 2.0 * r : robust_psi(r, delta);
+}
+
+// rho(r); HUBER operation by operation as robust_residual_kernel's h.
+__device__ __forceinline__ double smooth_rho(double r, int kind, double delta) {
+    if (kind == 0) return r * r;
+    const double z = __builtin_fabs(r);
+    if (kind == SPHRT_RESID_ABS) return z;
+    return z < delta ? (0.5 * z) * z : delta * (z - 0.5 * delta);
+}
+
+// One axis of voxel i (value v, coordinate c of n along the axis, element stride s): the lower
+// then the upper neighbour's w * rho'(v - d_nb) onto S, and the upper edge's w * rho onto `edges`
+// (every edge counted by its lower voxel; the wrap edge by the ring's last voxel).
+__device__ __forceinline__ void smooth_axis(const double* __restrict__ d, uint32_t i, double v,
+                                            uint32_t c, uint32_t n, uint32_t s, double w,
+                                            bool wrap, int kind, double delta, double& S,
+                                            double& edges) {
+    if (!(w > 0.0) || n < 2) return;
+    if (c > 0 || wrap) {
+        const double lo = d[c > 0 ? i - s : i + (n - 1) * s];
+        S += w * smooth_psi(v - lo, kind, delta);
+    }
+    if (c + 1 < n || wrap) {
+        const double hi = d[c + 1 < n ? i + s : i - (n - 1) * s];
+        S += w * smooth_psi(v - hi, kind, delta);
+        edges += w * smooth_rho(hi - v, kind, delta);
+    }
+}
+
+// S_i = sum over the present neighbours of w_ax * rho'(d_i - d_nb), in the fixed order t-, t+,
+// r-, r+, e-, e+, a-, a+ (the one function every caller's gradient comes from: the same bits);
+// `edges` receives the voxel's share of the penalty's sum.  Coordinates from 32-bit divisions
+// (n < 2^31); every neighbour index stays inside the voxel's own (t, r, e, a) block.
+__device__ __forceinline__ double smooth_sum(const double* __restrict__ d, uint32_t i, double v,
+                                             const SmoothDesc& p, double& edges) {
+    const uint32_t q1 = i / p.na, a = i - q1 * p.na;
+    const uint32_t q2 = q1 / p.ne, e = q1 - q2 * p.ne;
+    const uint32_t q3 = q2 / p.nr, r = q2 - q3 * p.nr;
+    const uint32_t tt = q3 % p.nt;
+    const uint32_t se = p.na, sr = p.ne * p.na, st = p.nr * sr;
+    double S = 0.0;
+    smooth_axis(d, i, v, tt, p.nt, st, p.wt, false, p.kind, p.delta, S, edges);
+    smooth_axis(d, i, v, r, p.nr, sr, p.wr, false, p.kind, p.delta, S, edges);
+    smooth_axis(d, i, v, e, p.ne, se, p.we, false, p.kind, p.delta, S, edges);
+    smooth_axis(d, i, v, a, p.na, 1u, p.wa, p.wrap != 0, p.kind, p.delta, S, edges);
+    return S;
+}
+
+// g_out = (g_in +) G, G_i = (S_i * inv_n) * lam — two roundings, in that order — and the partial
+// sums of the penalty's edges.  With part_neg the NegRegularizer's term is folded in as
+// neg_reg_kernel applies it (G - c_neg where d < 0; partial sums of |clamp(d, max=0)|), so that
+// g_out = g_in + (G + neg): the order autograd leaves for [fidelity, the two regularisers].
+// g_in may be g_out (each thread reads its own element first); d may not (neighbours are read).
+__global__ __launch_bounds__(kLossThreads) void smooth_reg_kernel(
+    const double* __restrict__ d, uint32_t n, SmoothDesc p, double inv_n, double lam, double c_neg,
+    const double* g_in, double* g_out, double* __restrict__ part_smooth,
+    double* __restrict__ part_neg) {
+    double acc = 0.0, acc_neg = 0.0;
+    for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
+         i += gridDim.x * kLossThreads) {
+        const double v = d[i];
+        const double S = smooth_sum(d, i, v, p, acc);
+        double h = (S * inv_n) * lam;
+        if (part_neg) {                                    // as neg_reg_kernel
+            const double c = v > 0.0 ? 0.0 : v;
+            acc_neg += __builtin_fabs(c);
+            if (v < 0.0) h = h - c_neg;
+        }
+        g_out[i] = g_in ? g_in[i] + h : h;
+    }
+    block_partial(acc, part_smooth);
+    if (part_neg) {
+        __syncthreads();                                   // (block_partial's LDS is reused)
+        block_partial(acc_neg, part_neg);
+    }
+}
+
 // Adam on float64 coefficients, with the NegRegularizer's gradient term and loss partials folded
 // in: one launch where the loop made three or more (neg_reg, the step-count add, the optimiser's
 // own launches).  Two arithmetics, each the per-element operation sequence of one of torch's
@@ -281,6 +374,44 @@ extern "C" int sphrt_neg_reg_f64(const double* d, int64_t n, double c_neg, doubl
     hipLaunchKernelGGL(neg_reg_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
                        (hipStream_t)stream, d, n, c_neg, g, partial_sums);
     return check_launch("neg_reg");
+}
+
+extern "C" int sphrt_smooth_reg_f64(const double* d, int64_t n_batch, int nt, int nr, int ne, int na,
+                                    double wt, double wr, double we, double wa, int kind,
+                                    double delta, int wrap_a, double inv_n, double lam,
+                                    double c_neg, const double* g_in, double* g_out,
+                                    double* part_smooth, double* part_neg, void* stream) {
+    const char* me = "sphrt_smooth_reg_f64";
+    if (nt < 1 || nr < 1 || ne < 1 || na < 1)
+        return fail("%s: axis lengths (%d, %d, %d, %d) must be >= 1", me, nt, nr, ne, na);
+    if (n_batch < 1) return fail("%s: empty volume (n_batch %lld)", me, (long long)n_batch);
+    const int64_t lim = (int64_t)1 << 31;
+    int64_t n = n_batch;                      // (every factor < 2^31: no int64 overflow below)
+    for (int len : {nt, nr, ne, na}) {
+        if (n >= lim) break;
+        n *= len;
+    }
+    if (n >= lim) return fail("%s: the volume must have fewer than 2^31 voxels", me);
+    for (double w : {wt, wr, we, wa})
+        if (!(w >= 0.0) || __builtin_isinf(w))           // (a NaN fails the compare)
+            return fail("%s: the axis weights must be finite and >= 0, not %g", me, w);
+    if (__builtin_isnan(inv_n) || __builtin_isinf(inv_n) || __builtin_isnan(lam) ||
+        __builtin_isinf(lam))
+        return fail("%s: inv_n and lam must be finite, not %g and %g", me, inv_n, lam);
+    double rd = 0.0;
+    if (kind != 0)
+        if (int e = refuse_robust(kind, delta, rd)) return e;
+    if (!part_smooth) return fail("%s: null part_smooth", me);
+    if (!g_out) return fail("%s: null g_out", me);
+    if (!d) return fail("%s: null density", me);
+    if (d == g_out) return fail("%s: d and g_out must not be the same buffer", me);
+    SmoothDesc p{(uint32_t)nt, (uint32_t)nr, (uint32_t)ne, (uint32_t)na, wt, wr, we, wa,
+                 kind, rd, wrap_a && na > 1};
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(smooth_reg_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, d, (uint32_t)n, p, inv_n, lam, c_neg, g_in, g_out,
+                       part_smooth, part_neg);
+    return check_launch("smooth_reg");
 }
 
 static int adam_launch(bool foreach, double* param, const double* grad, double* exp_avg,

@@ -157,11 +157,12 @@ class ShardedOperator:
 
 def _declined(loss_fns):
     """Does gd() keep these terms out of its direct loop, whatever retrieval._direct_plan takes
-    on one GPU: a tensor projection_mask, or a robust fidelity term (AbsLoss, HuberLoss) — only
-    the unmasked SquareLoss loop is worked out over ranks."""
-    from .loss import AbsLoss, HuberLoss
-    return any(isinstance(fn.projection_mask, tr.Tensor) or type(fn) in (AbsLoss, HuberLoss)
-               for fn in loss_fns)
+    on one GPU: a tensor projection_mask, a robust fidelity term (AbsLoss, HuberLoss) or a
+    SmoothRegularizer — only the unmasked SquareLoss loop with a NegRegularizer is worked out
+    over ranks."""
+    from .loss import AbsLoss, HuberLoss, SmoothRegularizer
+    return any(isinstance(fn.projection_mask, tr.Tensor)
+               or type(fn) in (AbsLoss, HuberLoss, SmoothRegularizer) for fn in loss_fns)
 
 
 def gd(f, y_local, model, coeffs=None, num_iterations=100, loss_fns=None, optim=tr.optim.Adam,

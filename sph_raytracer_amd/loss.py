@@ -3,6 +3,7 @@
 A loss is built once, weighted by multiplying with a scalar (``5 * SquareLoss()``), and called
 by ``gd()`` as ``loss(f, y, density, coeffs)``; the fidelity losses call the Operator ``f``.
 """
+import math
 import numbers
 
 import torch as t
@@ -121,6 +122,155 @@ class NegRegularizer(Loss):
 
     def compute(self, f, y, d, c):
         return t.mean(t.abs(_scaled(self.volume_mask, d.clip(max=0))))
+
+
+SMOOTH_KINDS = {'square': 0, 'abs': 1, 'huber': 2}   # 0, SPHRT_RESID_ABS, SPHRT_RESID_HUBER
+
+
+def _real(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+class SmoothRegularizer(Loss):
+    """Roughness of the density: a difference penalty over its trailing axes (r, e, a) and,
+    with ``time_weight``, the axis before them (a dynamic grid's time axis, or a channel axis);
+    any further leading axes are batch.  Not in the reference.
+
+        P(d) = (1/N) * sum_ax w_ax * sum_{edges i -> i+1 along ax} rho(d[i+1] - d[i])
+
+    with N = d.numel() and rho by ``kind``: ``'square'`` (r^2), ``'abs'`` (|r|: anisotropic total
+    variation) or ``'huber'`` (torch's huber_loss with ``delta``).  ``weights`` are (w_r, w_e,
+    w_a).  With ``wrap_a`` the azimuth ring closes — one more edge from the last azimuth bin to the
+    first, ``roll(d, -1, -1) - d``; None: it closes when the grid of the operator `f` spans 2 pi
+    in azimuth (to 1e-9 relative; no grid: open).  An axis of length 1 or of weight 0 contributes
+    nothing.
+
+    A contiguous float64 density on a GPU is evaluated by one HIP launch (csrc/loss.hip,
+    sphrt_smooth_reg_f64: value and gradient in one pass); anything else — CPU tensors, float32,
+    non-contiguous tensors, a differentiable backward — by the same formula in plain torch
+    (`formula`)."""
+
+    def __init__(self, weights=(1, 1, 1), time_weight=0, kind='square', delta=None, wrap_a=None,
+                 **kwargs):
+        try:
+            weights = tuple(weights)
+        except TypeError:
+            weights = ()
+        if len(weights) != 3 or not all(self._weight(w) for w in weights):
+            raise ValueError('SmoothRegularizer needs three weights (w_r, w_e, w_a), real numbers '
+                             f'that are finite and >= 0, not {weights!r}')
+        if not self._weight(time_weight):
+            raise ValueError('SmoothRegularizer needs a time_weight that is a real number, finite '
+                             f'and >= 0, not {time_weight!r}')
+        if not isinstance(kind, str) or kind not in SMOOTH_KINDS:
+            raise ValueError(f"kind must be 'square', 'abs' or 'huber', not {kind!r}")
+        if kind == 'huber':
+            if not (_real(delta) and delta > 0 and delta != float('inf')):
+                raise ValueError(f"kind='huber' needs a finite delta > 0, not {delta!r}")
+        elif delta is not None:
+            raise ValueError(f"delta belongs to kind='huber', not kind={kind!r}")
+        if wrap_a is not None and not isinstance(wrap_a, bool):
+            raise ValueError(f'wrap_a must be True, False or None, not {wrap_a!r}')
+        self.weights = tuple(float(w) for w in weights)
+        self.time_weight = float(time_weight)
+        self.smooth_kind = kind
+        self.delta = float(delta) if kind == 'huber' else None
+        self.wrap_a = wrap_a
+        super().__init__(**kwargs)
+
+    @staticmethod
+    def _weight(w):
+        return _real(w) and 0 <= w < float('inf')
+
+    def wraps(self, f):
+        """Does the azimuth ring close: ``wrap_a``, or inferred from the grid of `f`."""
+        if self.wrap_a is not None:
+            return self.wrap_a
+        grid = getattr(f, 'grid', None)
+        a_b = getattr(grid, 'a_b', None)
+        if a_b is None or len(a_b) < 2:
+            return False
+        span = abs(float(a_b[-1]) - float(a_b[0]))
+        return abs(span - 2 * math.pi) <= 1e-9 * (2 * math.pi)
+
+    def _rho(self, hi, lo):
+        if self.smooth_kind == 'square':
+            return (hi - lo) ** 2
+        if self.smooth_kind == 'abs':
+            return (hi - lo).abs()
+        return t.nn.functional.huber_loss(hi, lo, reduction='none', delta=self.delta)
+
+    def _axes(self, d):
+        """[(dim, weight)] of the axes that have edges, in the order t, r, e, a."""
+        if d.dim() < 3:
+            raise ValueError(f'SmoothRegularizer needs a density with axes (..., r, e, a), not '
+                             f'shape {tuple(d.shape)}')
+        axes = [(-4, self.time_weight)] if d.dim() >= 4 else []
+        axes += [(-3, self.weights[0]), (-2, self.weights[1]), (-1, self.weights[2])]
+        return [(dim, w) for dim, w in axes if w > 0 and d.shape[dim] > 1]
+
+    def formula(self, d, wrap):
+        """The penalty in plain torch (differentiable): narrow, roll, abs, huber_loss."""
+        total = d.new_zeros(())
+        for dim, w in self._axes(d):
+            n = d.shape[dim]
+            if dim == -1 and wrap:
+                hi, lo = t.roll(d, -1, -1), d
+            else:
+                hi, lo = d.narrow(dim, 1, n - 1), d.narrow(dim, 0, n - 1)
+            total = total + w * self._rho(hi, lo).sum()
+        return total / d.numel()
+
+    def _launch(self, d, wrap, lam, c_neg, g_in, g_out, part_smooth, part_neg):
+        """sphrt_smooth_reg_f64 over the contiguous float64 GPU density `d`."""
+        from . import _lib
+        lib = _lib.load()
+        timed = d.dim() >= 4 and self.time_weight > 0
+        nt = d.shape[-4] if timed else 1
+        nr, ne, na = d.shape[-3:]
+        _lib.check(lib.sphrt_smooth_reg_f64(
+            _lib.ptr(d), d.numel() // (nt * nr * ne * na), nt, nr, ne, na, self.time_weight,
+            *self.weights, SMOOTH_KINDS[self.smooth_kind], self.delta or 0.0, int(wrap),
+            1.0 / d.numel(), lam, c_neg, _lib.ptr(g_in), _lib.ptr(g_out), _lib.ptr(part_smooth),
+            _lib.ptr(part_neg), _lib.stream_of(d.device)), 'sphrt_smooth_reg_f64')
+
+    def compute(self, f, y, d, c):
+        d = _scaled(self.volume_mask, d)
+        wrap = self.wraps(f)
+        if isinstance(d, t.Tensor) and d.is_cuda and d.dtype == t.float64 and d.is_contiguous() \
+                and d.dim() >= 3 and d.numel() > 0:
+            return _SmoothFunction.apply(d, self, wrap)
+        return self.formula(d, wrap)
+
+
+class _SmoothFunction(t.autograd.Function):
+    """SmoothRegularizer on a contiguous float64 GPU density: the forward is one launch that
+    leaves the penalty's partial sums and its gradient G (lam = 1), the backward G * grad_out.
+    A backward that is itself differentiated (create_graph) comes from the torch formula."""
+
+    @staticmethod
+    def forward(ctx, d, reg, wrap):
+        from . import _lib
+        src = d.detach()
+        n_part = _lib.load().sphrt_loss_partials(src.numel())
+        part = t.empty(n_part, dtype=t.float64, device=src.device)
+        grad = t.empty_like(src)
+        with t.cuda.device(src.device):
+            reg._launch(src, wrap, 1.0, 0.0, None, grad, part, None)
+        ctx.reg, ctx.wrap, ctx.grad = reg, wrap, grad
+        ctx.save_for_backward(d)
+        return part.sum() / src.numel()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if t.is_grad_enabled():
+            d, = ctx.saved_tensors
+            with t.enable_grad():
+                src = d if d.requires_grad else d.detach().requires_grad_()
+                g, = t.autograd.grad(ctx.reg.formula(src, ctx.wrap), src, grad_out,
+                                     create_graph=True)
+            return g, None, None
+        return ctx.grad * grad_out, None, None
 
 
 class NegSumRegularizer(Loss):

@@ -10,7 +10,7 @@ import math
 
 import torch as t
 
-from .loss import AbsLoss, HuberLoss, NegRegularizer, SquareLoss
+from .loss import AbsLoss, HuberLoss, NegRegularizer, SmoothRegularizer, SquareLoss
 from .model import FullyDenseModel
 
 try:
@@ -126,9 +126,13 @@ def _direct_plan(f, y, model, coeffs, loss_fns, optim_vars):
     """The loss terms of a loop `_gd_direct` runs without autograd, or None.  It covers the
     examples/static_retrieval.py loop: a FullyDenseModel (the coefficients are the density) on a
     static Operator, one fidelity term — a SquareLoss, an AbsLoss or a HuberLoss, exactly those
-    types — and at most one NegRegularizer, scalar weights, no masks but the fidelity term's
-    projection_mask (`_ray_mask`: per-ray weights, a mask of bad pixels), the coefficients the
-    only optimised variable.  Anything else takes the autograd loop."""
+    types — at most one NegRegularizer and at most one SmoothRegularizer, scalar weights, no
+    masks but the fidelity term's projection_mask (`_ray_mask`: per-ray weights, a mask of bad
+    pixels), the coefficients the only optimised variable.  With all three terms the fidelity
+    term must come first in `loss_fns`: autograd accumulates the terms [t1, t2, t3] of the total
+    at the shared leaf as (g3 + g2) + g1, and the smooth kernel forms g_fid + (g_smooth + g_neg);
+    with the fidelity term second or third the sum would round otherwise, so that list is
+    declined (two terms commute: any order).  Anything else takes the autograd loop."""
     from .raytracer import Operator
     if not isinstance(f, Operator) or f.dynamic or f._csr is None or y is None:
         return None
@@ -174,9 +178,10 @@ def _robust_of(fid):
 
 def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
     """(fidelity term, NegRegularizer or None) when model, variables, measurements and loss terms
-    are those `_gd_direct` runs over the operator `f`, else None.  The fidelity term is exactly
-    one SquareLoss, AbsLoss or HuberLoss (`_FIDELITY`; a subclass may compute anything: the
-    autograd loop)."""
+    are those `_gd_direct` runs over the operator `f`, else None; with a SmoothRegularizer among
+    the terms, the 3-tuple (fidelity, NegRegularizer or None, SmoothRegularizer).  The fidelity
+    term is exactly one SquareLoss, AbsLoss or HuberLoss (`_FIDELITY`; a subclass may compute
+    anything: the autograd loop); with both regularisers it is the first term (`_direct_plan`)."""
     if type(model) is not FullyDenseModel or hasattr(model, 'proj'):
         return None
     if len(optim_vars) != 1 or optim_vars[0] is not coeffs or coeffs.dtype != t.float64:
@@ -187,7 +192,7 @@ def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
             and tuple(y.shape) == tuple(f._ray_shape)):
         # (other devices, or a y the reference's SquareLoss would broadcast: the autograd loop)
         return None
-    sq = neg = None
+    sq = neg = smooth = None
     for fn in loss_fns:
         if not (fn.use_grad and isinstance(fn.lam, (int, float)) and not isinstance(fn.lam, bool)
                 and _unit(fn.volume_mask)):
@@ -199,11 +204,17 @@ def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
             sq = fn
         elif type(fn) is NegRegularizer and neg is None:
             neg = fn
+        elif type(fn) is SmoothRegularizer and smooth is None:
+            smooth = fn
         else:
             return None
     if sq is None:
         return None
-    return sq, neg
+    if smooth is None:
+        return sq, neg
+    if neg is not None and loss_fns[0] is not sq:
+        return None     # ((g3 + g2) + g1: only a leading fidelity term gives g_fid + (the rest))
+    return sq, neg, smooth
 
 
 def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, reduce=None,
@@ -238,6 +249,12 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     Gradient of lam * mean(|clip(d, max=0)|): -(lam / N) where d < 0, else 0 (sign(0) = 0).
     The two are summed (IEEE addition commutes, so the order autograd accumulates them in does
     not matter) and handed to the optimiser as coeffs.grad.
+    With a SmoothRegularizer (a 3-tuple plan): its Function's backward is G * lam with
+    G = (S * (1 / N)) * 1, i.e. (S * inv_n) * lam, and autograd sums three terms as
+    (g_smooth + g_neg) + g_fid (`_direct_plan`).  One sphrt_smooth_reg_f64 launch after the
+    adjoint forms g = g + (G + neg) in place — the NegRegularizer's term as above, folded in —
+    and leaves both regularisers' partial sums; the Adam launch then runs without a regulariser
+    (c_neg = 0), and for another optimiser the launch stands in for sphrt_neg_reg_f64.
 
     Data-parallel use (distributed.gd): `f` is this rank's operator over its share of the views,
     `y` its share of the measurements, `n_total` the size of the whole stack (the SquareLoss
@@ -247,7 +264,8 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     from . import _lib
     from .raytracer import MatrixFreeOperator
     fused = isinstance(f, MatrixFreeOperator)
-    sq, neg = plan
+    sq, neg = plan[:2]
+    smooth = plan[2] if len(plan) > 2 else None
     losses = {fn: [] for fn in loss_fns}
     y.requires_grad_()                 # (the reference's own side effect on y)
     # y as measured: a float32 y is promoted inside the residual kernel (exactly, as y - f(d)
@@ -319,6 +337,10 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     rows = max(num_iterations, 1)
     part_sq = t.empty((rows, ps), dtype=t.float64, device=coeffs.device)
     part_neg = t.empty((rows, pn), dtype=t.float64, device=coeffs.device) if neg is not None else None
+    part_smooth = smooth_wrap = None
+    if smooth is not None:
+        part_smooth = t.empty((rows, pn), dtype=t.float64, device=coeffs.device)
+        smooth_wrap = smooth.wraps(f)
     done = 0
 
     def scaled(sums, n, lam):
@@ -388,7 +410,15 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                                          trace_order=order is not None)
                 if reduce is not None:
                     reduce(g)          # data-parallel: the sum of every rank's adjoint
-                if step is not None:
+                if smooth is not None:
+                    # g = g + (G_smooth + g_neg) in place and both regularisers' partial sums
+                    # (sphrt_smooth_reg_f64: the NegRegularizer's term folded in, so the
+                    # optimiser step below takes none)
+                    smooth._launch(d, smooth_wrap, smooth.lam, c_neg, g, g, part_smooth[it],
+                                   part_neg[it] if neg is not None else None)
+                    if step is not None:
+                        step(g, 0.0, None, stream, staged[0] if staged is not None else None)
+                elif step is not None:
                     # the regulariser's gradient term and loss partials inside the Adam launch
                     step(g, c_neg, part_neg[it] if neg is not None else None, stream,
                          staged[0] if staged is not None else None)
@@ -400,6 +430,8 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 if progress_bar:      # (this rank's share of the SquareLoss when data-parallel)
                     fv = float(scaled(part_sq[it].sum(), n_norm, sq.lam))
                     rv = float(scaled(part_neg[it].sum(), n_vox, neg.lam)) if neg is not None else 0
+                    if smooth is not None:
+                        rv += float(scaled(part_smooth[it].sum(), n_vox, smooth.lam))
                     bar.describe(f'F:{fv:.1e} R:{rv:.1e} O:0')
                 if step is None:
                     coeffs.grad = g
@@ -415,6 +447,8 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
         reduce(sums)
     if neg is not None:
         sums = t.cat([sums, part_neg[:done].sum(-1)])
+    if smooth is not None:
+        sums = t.cat([sums, part_smooth[:done].sum(-1)])
     # the return value's forward goes out before the readback waits (best is these coefficients
     # unless no iteration's total was finite, below)
     y_best = f(coeffs)
@@ -423,7 +457,9 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     host = sums.cpu().tolist()
     losses[sq] = [scaled(v, n_norm, sq.lam) for v in host[:done]]
     if neg is not None:
-        losses[neg] = [scaled(v, n_vox, neg.lam) for v in host[done:]]
+        losses[neg] = [scaled(v, n_vox, neg.lam) for v in host[done:2 * done]]
+    if smooth is not None:
+        losses[smooth] = [scaled(v, n_vox, smooth.lam) for v in host[len(host) - done:]]
     # the reference's bookkeeping: the coefficients once some iteration's total was < inf
     totals = [sum(v) for v in zip(*(losses[fn] for fn in loss_fns))]
     best = coeffs if any(v < float('inf') for v in totals) else None
