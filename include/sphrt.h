@@ -573,6 +573,41 @@ int sphrt_adam_foreach_neg_f64(double *param, const double *grad, double *exp_av
                                double c_neg, double *partial_sums, const sphrt_csr *stage_of,
                                void *stream);
 
+/* ---- conjugate gradients: the vector side of an iteration (csrc/loss.hip; retrieval.cg) ------
+ * For N x = b with N symmetric positive semi-definite, an iteration is h = N p (the operator's
+ * entries and sphrt_smooth_reg_f64), then these three launches over the n elements of x, r, p, h
+ * (float64, distinct buffers).  alpha and beta never reach the host: a launch leaves its
+ * workgroups' partial sums of a dot product (the launch shape and partition of the entries
+ * above), and the next launch has every workgroup sum those n_part <= 1024 partials itself in
+ * one fixed order, so the scalar has the same bits in every workgroup:
+ *   SUM(part): thread t of 256 adds part[t], part[t + 256], part[t + 512], part[t + 768] (those
+ *   below n_part), in that order, onto +0.0; the 64 values of a wave by the xor butterfly 32,
+ *   16, 8, 4, 2, 1 (v += v of lane ^ off; both lanes of a pair form the same sum); the four wave
+ *   totals, in order, onto +0.0.
+ * Every product feeding a sum is a plain multiply and every update one fma, whatever
+ * -ffp-contract says; inf, NaN and denormals are not special-cased beyond the guards written
+ * below (0 * inf is NaN, also with alpha = 0).  rr_stop points to one float64 on the device, the
+ * squared residual norm at which the solve freezes; NULL: never.  Each entry fails on the host,
+ * before any launch and without reading a pointer, on n <= 0, on a null buffer (rr_stop may be
+ * NULL) and on n_part != the partial count of a launch over n elements.
+ *
+ *   h[i] = fma(c_damp, p[i], h[i]);  part_php: partial sums of p[i] * h[i] (the new h)        */
+int sphrt_cg_curvature_f64(const double *p, double *h, int64_t n, double c_damp,
+                           double *part_php, void *stream);
+/*   RR = SUM(part_rr), PHP = SUM(part_php)
+ *   alpha = (RR <= *rr_stop || !(PHP > 0) || !isfinite(RR / PHP)) ? 0 : RR / PHP
+ *   x[i] = fma(alpha, p[i], x[i]);  r[i] = fma(-alpha, h[i], r[i])
+ *   part_rr_new: partial sums of r[i] * r[i] (the new r); it may not be part_rr or part_php    */
+int sphrt_cg_update_f64(double *x, double *r, const double *p, const double *h, int64_t n,
+                        const double *part_rr, const double *part_php, int64_t n_part,
+                        const double *rr_stop, double *part_rr_new, void *stream);
+/*   RR_new = SUM(part_rr_new), RR_old = SUM(part_rr)
+ *   beta = (RR_old <= *rr_stop || !(RR_old > 0)) ? 0 : RR_new / RR_old
+ *   p[i] = fma(beta, p[i], r[i])                                                              */
+int sphrt_cg_direction_f64(double *p, const double *r, int64_t n,
+                           const double *part_rr_new, const double *part_rr, int64_t n_part,
+                           const double *rr_stop, void *stream);
+
 /* ---- fused no-store mode: trace + integrate in one pass (nothing persisted) --------------- */
 int sphrt_trace_integrate_f32(const sphrt_plan *plan, const sphrt_rays *rays,
                               const float *density, int64_t n_chan, int64_t chan_stride,

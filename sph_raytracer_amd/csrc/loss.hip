@@ -13,6 +13,9 @@
 // those of the autograd loop.  The means are deterministic (fixed per-thread strides, a fixed
 // reduction tree, the partials summed in a fixed order) but their order differs from
 // torch.mean's: loss values agree with it to rounding (~1e-16).
+//
+// The vector side of retrieval.cg's iteration (two dot products, alpha, beta, three updates) is
+// here too, as three launches of the same shape that pass their scalars through partial sums.
 #include "common.hpp"
 #include "stage.hpp"
 
@@ -296,9 +299,127 @@ __global__ __launch_bounds__(kLossThreads) void adam_neg_kernel(
     if (part) block_partial(acc, part);
 }
 
+// ---- conjugate gradients (retrieval.cg): the vector side of an iteration in three launches ------
+// The scalars alpha and beta are never on the host: each launch leaves its workgroups' partial
+// sums of a dot product, and the next one has every workgroup sum those partials itself, all in
+// the same fixed order, so the scalar has the same bits in every workgroup:
+//   thread t adds the partials t, t + 256, t + 512, t + 768 (those below n_part <= 1024), in
+//   that order, onto +0.0; the wave's 64 values by the xor butterfly 32, 16, 8, 4, 2, 1 (both
+//   lanes of a pair form the same sum: IEEE addition commutes); the four wave totals, in order,
+//   onto +0.0.
+// Two sums at once (a launch needs at most two); every thread returns with both totals.
+__device__ __forceinline__ void block_totals(const double* __restrict__ pa,
+                                             const double* __restrict__ pb, int n_part,
+                                             double& ta, double& tb) {
+    __shared__ double sh[2][kLossThreads / 64];
+    double a = 0.0, b = 0.0;
+    for (int j = threadIdx.x; j < n_part; j += kLossThreads) {
+        a += pa[j];
+        b += pb[j];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_xor(a, off);
+        b += __shfl_xor(b, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][threadIdx.x >> 6] = a;
+        sh[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    ta = tb = 0.0;
+    for (int i = 0; i < kLossThreads / 64; ++i) {
+        ta += sh[0][i];
+        tb += sh[1][i];
+    }
+}
+
+// h = c_damp * p + h (one fma: the damping term of N p onto A^T(s A p) + G p) and the partial
+// sums of p * h over the new h.
+__global__ __launch_bounds__(kLossThreads) void cg_curvature_kernel(
+    const double* __restrict__ p, double* __restrict__ h, int64_t n, double c_damp,
+    double* __restrict__ part) {
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * kLossThreads) {
+        const double pi = p[i];
+        const double hi = fma(c_damp, pi, h[i]);
+        h[i] = hi;
+        acc += pi * hi;
+    }
+    block_partial(acc, part);
+}
+
+// alpha = RR / PHP — 0 once RR <= *rr_stop (the solve is frozen), when PHP is not > 0 (a zero
+// right-hand side; a NaN fails the compare) and when the quotient is not finite; x += alpha p,
+// r -= alpha h (one fma each) and the partial sums of the new r * r.  The thread's first
+// elements are loaded before the partials are summed (their latencies overlap).
+__global__ __launch_bounds__(kLossThreads) void cg_update_kernel(
+    double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
+    const double* __restrict__ h, int64_t n, const double* __restrict__ part_rr,
+    const double* __restrict__ part_php, int n_part, const double* __restrict__ rr_stop,
+    double* __restrict__ part_out) {
+    const int64_t i0 = (int64_t)blockIdx.x * kLossThreads + threadIdx.x;
+    double x0 = 0.0, r0 = 0.0, p0 = 0.0, h0 = 0.0;
+    if (i0 < n) {
+        x0 = x[i0];
+        r0 = r[i0];
+        p0 = p[i0];
+        h0 = h[i0];
+    }
+    double RR, PHP;
+    block_totals(part_rr, part_php, n_part, RR, PHP);
+    const double q = RR / PHP;
+    const bool off = (rr_stop && RR <= *rr_stop) || !(PHP > 0.0) || !__builtin_isfinite(q);
+    const double alpha = off ? 0.0 : q;
+    double acc = 0.0;
+    for (int64_t i = i0; i < n; i += (int64_t)gridDim.x * kLossThreads) {
+        const bool first = i == i0;
+        const double xi = first ? x0 : x[i], ri = first ? r0 : r[i];
+        const double pi = first ? p0 : p[i], hi = first ? h0 : h[i];
+        x[i] = fma(alpha, pi, xi);
+        const double rn = fma(-alpha, hi, ri);
+        r[i] = rn;
+        acc += rn * rn;
+    }
+    block_partial(acc, part_out);
+}
+
+// beta = RR_new / RR_old — 0 once RR_old <= *rr_stop and when RR_old is not > 0; p = beta p + r
+// (one fma).
+__global__ __launch_bounds__(kLossThreads) void cg_direction_kernel(
+    double* __restrict__ p, const double* __restrict__ r, int64_t n,
+    const double* __restrict__ part_new, const double* __restrict__ part_old, int n_part,
+    const double* __restrict__ rr_stop) {
+    const int64_t i0 = (int64_t)blockIdx.x * kLossThreads + threadIdx.x;
+    double p0 = 0.0, r0 = 0.0;
+    if (i0 < n) {
+        p0 = p[i0];
+        r0 = r[i0];
+    }
+    double RRn, RRo;
+    block_totals(part_new, part_old, n_part, RRn, RRo);
+    const bool off = (rr_stop && RRo <= *rr_stop) || !(RRo > 0.0);
+    const double beta = off ? 0.0 : RRn / RRo;
+    for (int64_t i = i0; i < n; i += (int64_t)gridDim.x * kLossThreads) {
+        const bool first = i == i0;
+        p[i] = fma(beta, first ? p0 : p[i], first ? r0 : r[i]);
+    }
+}
+
 static unsigned loss_grid(int64_t n) {
     const int64_t b = (n + kLossThreads - 1) / kLossThreads;
     return (unsigned)(b < kLossMaxBlocks ? (b > 0 ? b : 1) : kLossMaxBlocks);
+}
+
+// The host refusals the three cg entries share: the length and the count of partial sums that a
+// launch over that length leaves (nothing is dereferenced).
+static int refuse_cg(const char* me, int64_t n, int64_t n_part, bool check_part) {
+    if (n <= 0) return fail("%s: empty vector (n %lld)", me, (long long)n);
+    if (check_part && n_part != (int64_t)loss_grid(n))
+        return fail("%s: n_part %lld, a launch over %lld elements leaves %u partial sums", me,
+                    (long long)n_part, (long long)n, loss_grid(n));
+    return 0;
 }
 
 }  // namespace sphrt
@@ -465,4 +586,42 @@ extern "C" int sphrt_adam_foreach_neg_f64(double* param, const double* grad, dou
     return adam_launch(true, param, grad, exp_avg, exp_avg_sq, n, step_size, beta1, beta2, eps,
                        weight_decay, bc2_sqrt, c_neg, partial_sums, stage_of, stream,
                        "sphrt_adam_foreach_neg_f64");
+}
+
+extern "C" int sphrt_cg_curvature_f64(const double* p, double* h, int64_t n, double c_damp,
+                                      double* part_php, void* stream) {
+    const char* me = "sphrt_cg_curvature_f64";
+    if (int e = refuse_cg(me, n, 0, false)) return e;
+    if (!p || !h || !part_php) return fail("%s: null buffer", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(cg_curvature_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, p, h, n, c_damp, part_php);
+    return check_launch("cg_curvature");
+}
+
+extern "C" int sphrt_cg_update_f64(double* x, double* r, const double* p, const double* h,
+                                   int64_t n, const double* part_rr, const double* part_php,
+                                   int64_t n_part, const double* rr_stop, double* part_rr_new,
+                                   void* stream) {
+    const char* me = "sphrt_cg_update_f64";
+    if (int e = refuse_cg(me, n, n_part, true)) return e;
+    if (!x || !r || !p || !h || !part_rr || !part_php || !part_rr_new)
+        return fail("%s: null buffer", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(cg_update_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, x, r, p, h, n, part_rr, part_php, (int)n_part,
+                       rr_stop, part_rr_new);
+    return check_launch("cg_update");
+}
+
+extern "C" int sphrt_cg_direction_f64(double* p, const double* r, int64_t n,
+                                      const double* part_rr_new, const double* part_rr,
+                                      int64_t n_part, const double* rr_stop, void* stream) {
+    const char* me = "sphrt_cg_direction_f64";
+    if (int e = refuse_cg(me, n, n_part, true)) return e;
+    if (!p || !r || !part_rr_new || !part_rr) return fail("%s: null buffer", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(cg_direction_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, p, r, n, part_rr_new, part_rr, (int)n_part, rr_stop);
+    return check_launch("cg_direction");
 }

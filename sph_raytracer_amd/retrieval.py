@@ -4,6 +4,10 @@ Every iteration is one Operator forward per fidelity loss plus one backward, i.e
 and adjoint HIP kernels on the cached trace; the optimiser step is plain PyTorch.  The
 examples/static_retrieval.py loop (FullyDenseModel, SquareLoss + NegRegularizer) runs the same
 arithmetic without autograd (_gd_direct): the same iterates, a quarter of the launches.
+
+`cg` (not in the reference) solves the totals that are quadratic — a SquareLoss, a square
+SmoothRegularizer, a damping term — as a linear system by conjugate gradients: the same operator
+launches per iteration, three csrc/loss.hip launches for the vector side, no learning rate.
 """
 import ctypes
 import math
@@ -529,3 +533,320 @@ def _split_adam(opt, coeffs):
             _lib.ptr(flat), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), flat.numel(), step_size, b1, b2,
             eps, wd, bc2_sqrt, c_neg, _lib.ptr(part), stage, stream), 'sphrt_adam_foreach_neg_f64')
     return step
+
+
+# ---- conjugate gradients ------------------------------------------------------------------------
+
+def cg(f, y, loss_fns=[SquareLoss()], x0=None, num_iterations=50, damp=0.0, tol=0.0,
+       progress_bar=False):
+    """Minimise, by conjugate gradients, the total `gd` minimises for the same `loss_fns` when
+    that total is quadratic:
+
+        J(x) = lam_f * mean(w * (y - f(x))^2) + lam_s * SmoothRegularizer(kind='square')(x)
+               + damp * mean(x^2)
+
+    -> (x, f(x), info).  No learning rate: grad J(x) = N x - b with N = A^T diag(s) A + G + c I
+    symmetric positive semi-definite, s = 2 (lam_f / M) w, c = 2 damp / V (M = y.numel(),
+    V = x.numel()), G the smooth term's (linear) gradient and b = A^T(s y); the solve starts at
+    `x0` (default: zeros of f.grid.shape, float64) with r_0 = -grad J(x0) and runs
+    `num_iterations` iterations.  Once |r_k|^2 <= tol^2 |r_0|^2 the iteration freezes (alpha =
+    beta = 0 from then on: x no longer changes); nothing is read back during the loop, so there
+    is no early exit, and tol = 0 never freezes.  info = {'residual': [|r_k| / |r_0| for k = 0 ..
+    num_iterations] (0.0 where r_k is exactly zero), 'converged_at': the first k at or under
+    tol, or None}.
+
+    `loss_fns`: exactly one SquareLoss (that type itself; scalar lam, unit volume_mask, a
+    projection_mask that is 1 or a tensor `gd`'s direct loop would weigh the residual with) and at
+    most one SmoothRegularizer(kind='square') (scalar lam, unit masks).  Anything else is not
+    quadratic or not known to be, and raises ValueError naming the term.
+
+    A static Operator (with its trace) or a static MatrixFreeOperator, float32 / float64
+    measurements of the operator's ray shape on its GPU and an `x0` that is None or a contiguous
+    float64 grid.shape tensor there run `_cg_direct`: the operator's own launches and three
+    csrc/loss.hip launches per iteration, the whole solve enqueued without a host sync and —
+    over an Operator, or a MatrixFreeOperator with `deterministic` set — bitwise reproducible.
+    Everything else (CPU tensors, other operators, dynamic grids, other dtypes) runs the same
+    algorithm in plain torch (`_cg_generic`)."""
+    sq, smooth = _cg_terms(y, loss_fns, damp, tol, num_iterations)
+    bar = _Bar(range(num_iterations), progress_bar)
+    if _cg_is_direct(f, y, x0):
+        return _cg_direct(f, y, sq, smooth, x0, num_iterations, float(damp), float(tol), bar)
+    return _cg_generic(f, y, sq, smooth, x0, num_iterations, float(damp), float(tol), bar)
+
+
+def _cg_terms(y, loss_fns, damp, tol, num_iterations):
+    """(the SquareLoss, the SmoothRegularizer or None) of a total `cg` solves; ValueError naming
+    what it does not."""
+    if not isinstance(y, t.Tensor):
+        raise ValueError(f'cg needs measurements y as a tensor, not {type(y).__name__}')
+    for name, v in (('damp', damp), ('tol', tol)):
+        if not _number(v) or not 0 <= v < float('inf'):
+            raise ValueError(f'cg needs a finite {name} >= 0, not {v!r}')
+    if isinstance(num_iterations, bool) or not isinstance(num_iterations, int) \
+            or num_iterations < 0:
+        raise ValueError(f'cg needs num_iterations as an integer >= 0, not {num_iterations!r}')
+    sq = smooth = None
+    for fn in loss_fns:
+        name = type(fn).__name__
+        if type(fn) is SquareLoss:
+            if sq is not None:
+                raise ValueError('cg solves for one SquareLoss, not two')
+            sq = fn
+        elif type(fn) is SmoothRegularizer:
+            if smooth is not None:
+                raise ValueError('cg solves with at most one SmoothRegularizer, not two')
+            if fn.smooth_kind != 'square':
+                raise ValueError(f"cg needs a quadratic total: SmoothRegularizer(kind="
+                                 f"{fn.smooth_kind!r}) is not (kind='square' is)")
+            smooth = fn
+        else:
+            raise ValueError(f'cg needs a quadratic total of one SquareLoss and at most one '
+                             f"SmoothRegularizer(kind='square'): {name} is neither (gd takes it)")
+        if not fn.use_grad:
+            raise ValueError(f'cg: {name}(use_grad=False) is a monitor, not a term of the total')
+        if not _number(fn.lam) or not math.isfinite(fn.lam):
+            raise ValueError(f'cg needs a finite scalar lam, not {name}.lam = {fn.lam!r}')
+        if not _unit(fn.volume_mask):
+            raise ValueError(f'cg does not take a volume_mask ({name})')
+        if not _unit(fn.projection_mask) and not (fn is sq and _ray_mask(fn.projection_mask, y)):
+            raise ValueError(f'cg: the projection_mask of {name} must be 1' + (
+                ' or a bool / float32 / float64 tensor on the device of y that broadcasts to '
+                'its shape' if fn is sq else ''))
+    if sq is None:
+        raise ValueError('cg needs one SquareLoss among loss_fns')
+    return sq, smooth
+
+
+def _cg_is_direct(f, y, x0):
+    """Does `_cg_direct` run this solve (`cg`'s docstring)."""
+    from .raytracer import MatrixFreeOperator, Operator
+    if type(f) is Operator:
+        if f.dynamic or f.grid.dynamic or f._csr is None:
+            return False
+    elif type(f) is MatrixFreeOperator:
+        if f.dynamic or f.grid.dynamic:
+            return False
+    else:
+        return False
+    if not (y.is_cuda and y.device == f._cdev and y.dtype in (t.float32, t.float64)
+            and tuple(y.shape) == tuple(f._ray_shape)):
+        return False
+    return x0 is None or (isinstance(x0, t.Tensor) and x0.device == f._cdev
+                          and x0.dtype == t.float64 and x0.is_contiguous()
+                          and tuple(x0.shape) == tuple(f.grid.shape))
+
+
+def _cg_info(rr, stop):
+    """`cg`'s info from the squared residual norms of k = 0 .. K and the freeze threshold (host
+    floats; stop None: tol = 0)."""
+    rr0 = rr[0]
+    hist = [0.0 if v == 0 else math.sqrt(v / rr0) if rr0 > 0 else float('nan') for v in rr]
+    at = None if stop is None else next((k for k, v in enumerate(rr) if v <= stop), None)
+    return {'residual': hist, 'converged_at': at}
+
+
+def _cg_generic(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
+    """`cg` in plain torch, through f(x) and f._apply_adjoint alone: the specification of
+    `_cg_direct` (the same guards in the same places; sums in torch's order) and what runs on
+    the CPU.  Every scalar stays a 0-dim tensor on the device: no sync inside the loop."""
+    with t.no_grad():
+        yd = y.detach()
+        x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=yd.device) if x0 is None \
+            else t.as_tensor(x0).detach().clone()
+        dshape, dtype, dev = tuple(x.shape), x.dtype, x.device
+        c_sq, c = sq.lam / yd.numel(), 2 * damp / x.numel()
+        s = 2 * c_sq if _unit(sq.projection_mask) else \
+            (c_sq * sq.projection_mask.detach().to(t.promote_types(yd.dtype, dtype))) * 2
+
+        def smooth_grad(d):
+            # (linear in d: the square kind's gradient, lam and 1 / V included)
+            with t.enable_grad():
+                leaf = d.detach().requires_grad_()
+                g, = t.autograd.grad(smooth(f, yd, leaf, leaf), leaf)
+            return g
+
+        def gradient(d, m):
+            """A^T(s (A d - m)) + G d + c d: grad J(d) with m = y, N d with m = None."""
+            q = f(d)
+            h = f._apply_adjoint(s * (q if m is None else q - m), dshape, dtype, dev)
+            if smooth is not None:
+                h = h + smooth_grad(d)
+            return t.add(h, d, alpha=c)
+
+        def frozen(v):
+            return v <= stop if stop is not None else t.zeros_like(v, dtype=t.bool)
+
+        r = -gradient(x, yd)
+        p = r.clone()
+        rr = (r * r).sum()
+        stop = rr * (tol * tol) if tol > 0 else None
+        zero, rrs = t.zeros_like(rr), [rr]
+        try:
+            for _ in bar:
+                h = gradient(p, None)
+                php = (p * h).sum()
+                q = rr / php
+                alpha = t.where(frozen(rr) | ~(php > 0) | ~t.isfinite(q), zero, q)
+                x = x + alpha * p
+                r = r - alpha * h
+                rr_new = (r * r).sum()
+                beta = t.where(frozen(rr) | ~(rr > 0), zero, rr_new / rr)
+                p = r + beta * p
+                rr = rr_new
+                rrs.append(rr)
+        except KeyboardInterrupt:
+            pass
+        y_hat = f(x)
+        host = t.stack(rrs + ([stop] if stop is not None else [])).cpu().tolist()
+    return x, y_hat, _cg_info(host[:len(rrs)], host[-1] if stop is not None else None)
+
+
+def _kernel_sum(part):
+    """The sum every workgroup of the cg kernels forms of a row of partial sums (SUM of
+    include/sphrt.h, csrc/loss.hip block_totals), restated with elementwise torch adds in the
+    same order: the same bits, for each row of `part` (..., n_part <= 1024).  Threads past
+    n_part hold +0.0, and x + 0.0 is x for every x the first `0.0 +` can leave."""
+    rows = part.reshape(-1, part.shape[-1])
+    pad = t.zeros((rows.shape[0], 4, 256), dtype=part.dtype, device=part.device)
+    pad.view(rows.shape[0], -1)[:, :rows.shape[1]] = rows
+    v = (((0.0 + pad[:, 0]) + pad[:, 1]) + pad[:, 2]) + pad[:, 3]       # a thread's slice
+    v = v.view(-1, 4, 64)
+    for half in (32, 16, 8, 4, 2, 1):                                   # lane 0 of the butterfly
+        v = v[..., :half] + v[..., half:2 * half]
+    v = v[..., 0]
+    return ((((0.0 + v[:, 0]) + v[:, 1]) + v[:, 2]) + v[:, 3]).reshape(part.shape[:-1])
+
+
+def _cg_direct(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
+    """`cg` on the operator's own entries (`_cg_is_direct`).  An iteration is h = N p — over a
+    MatrixFreeOperator one trace (`_normal_into` against zero measurements: q = A p and
+    A^T(s q)), over an Operator the loop's forward, the residual kernel against zero
+    measurements (s q in the adjoint's order) and the adjoint; then, with a smooth term, one
+    sphrt_smooth_reg_f64 launch (h += G p) — followed by three csrc/loss.hip launches:
+    sphrt_cg_curvature_f64 (h += c p, partial sums of p h), sphrt_cg_update_f64 (alpha from the
+    partial sums; x += alpha p, r -= alpha h, partial sums of r r) and sphrt_cg_direction_f64
+    (beta; p = r + beta p).  alpha, beta and the freeze live on the device, formed by every
+    workgroup from the partial sums in one fixed order (`_kernel_sum` restates it), so nothing
+    is read back before the loop ends; the residual history is then one row of partial sums per
+    iteration.  The first residual goes through the same launches: g = grad J(x0) from the
+    operator's entries against y, the smooth launch and the curvature launch on x0, and an update
+    launch with alpha = 1 on zeroed r and p (r = -g, x unchanged, the partial sums of r r)."""
+    from . import _lib
+    from .raytracer import MatrixFreeOperator, _scale_max
+    lib = _lib.load()
+    fused = isinstance(f, MatrixFreeOperator)
+    dev, f64 = f._cdev, t.float64
+    yd = y.detach().contiguous()
+    y_f64 = int(yd.dtype == f64)
+    with t.no_grad(), t.cuda.device(dev):
+        x = t.zeros(tuple(f.grid.shape), dtype=f64, device=dev) if x0 is None \
+            else x0.detach().clone()
+        n_meas, n_vox = yd.numel(), x.numel()
+        c_sq, c = sq.lam / n_meas, 2 * damp / n_vox
+        w_res = s_res = None
+        if isinstance(sq.projection_mask, t.Tensor):     # as _gd_direct forms them
+            w_res = sq.projection_mask.detach().to(f64).expand(yd.shape).contiguous().reshape(-1)
+            s_res = (c_sq * w_res) * 2
+        r, p = t.zeros_like(x), t.zeros_like(x)
+        pn, ps = lib.sphrt_loss_partials(n_vox), lib.sphrt_loss_partials(n_meas)
+        part_rr = t.empty((num_iterations + 1, pn), dtype=f64, device=dev)
+        part_php = t.empty(pn, dtype=f64, device=dev)
+        part_tmp = t.empty(max(pn, ps), dtype=f64, device=dev)   # (sums nobody reads)
+        wrap = smooth.wraps(f) if smooth is not None else None
+        q_buf = t.empty(n_meas, dtype=f64, device=dev)
+        zero_m = t.zeros(n_meas, dtype=f64, device=dev)
+        if fused:
+            m64 = yd.to(f64).reshape(-1)
+            weighted = None if s_res is None else \
+                (s_res, _scale_max(s_res) if f.deterministic else None)
+            fixed = (f._fixed_buffers(),) if f.deterministic else ()
+            h_buf = t.empty_like(x)
+
+            def normal(d, against_y):
+                """A^T(s (A d - m)), m = y or 0, into h_buf from one trace."""
+                if not fixed:
+                    h_buf.zero_()
+                f._normal_into(d, m64 if against_y else zero_m, 2 * c_sq, q_buf, h_buf, *fixed,
+                               weighted=weighted)
+                return h_buf
+        else:
+            # the loop's forward descriptor, the adjoint's input order and the measurements in
+            # that order, as _gd_direct sets them up (the brick-staged forward packs d itself)
+            staged = f._stage_for_loop(f64)
+            if staged is not None and f._csr['n'] != n_meas:
+                staged = None
+            order = f._adjoint_trace_order()
+            if order is not None and order.numel() != n_meas:
+                order = None
+            loop_desc = staged[0] if staged is not None else None
+            y_res, res_order, keep_rows = yd.reshape(-1), order, None
+            if order is not None:
+                sd = loop_desc if loop_desc is not None else f._loop_descriptor(f64)
+                keep_rows = f._trace_position_rows(sd) if sd is not None else None
+                if keep_rows is not None:
+                    loop_desc = sd
+                    y_res, res_order = y_res.index_select(0, f._ray_id_long()), None
+                    if w_res is not None:
+                        w_res, s_res = (v.index_select(0, f._ray_id_long())
+                                        for v in (w_res, s_res))
+            rs_buf = t.empty(n_meas, dtype=f64, device=dev)
+
+            def normal(d, against_y):
+                """A^T(s (A d - m)), m = y or 0: forward, scaled residual, adjoint."""
+                stream = _lib.stream_of(dev)
+                if loop_desc is not None:
+                    f._forward_staged(d, q_buf, loop_desc)
+                    q = q_buf
+                else:
+                    q = f(d).reshape(-1)
+                m, m_f64 = (y_res, y_f64) if against_y else (zero_m, 1)
+                if w_res is None:
+                    _lib.check(lib.sphrt_sq_residual_f64(
+                        _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, 2 * c_sq, _lib.ptr(res_order),
+                        _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream), 'sphrt_sq_residual_f64')
+                else:
+                    _lib.check(lib.sphrt_wsq_residual_f64(
+                        _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, _lib.ptr(s_res), _lib.ptr(w_res),
+                        _lib.ptr(res_order), _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream),
+                        'sphrt_wsq_residual_f64')
+                return f._apply_adjoint(rs_buf.view(yd.shape), tuple(d.shape), d.dtype, dev,
+                                        trace_order=order is not None)
+
+        def curvature(d, against_y):
+            """h = A^T(s (A d - m)) + G d + c d and the partial sums of d h (part_php)."""
+            h = normal(d, against_y)
+            if smooth is not None:
+                smooth._launch(d, wrap, smooth.lam, 0.0, h, h, part_tmp, None)
+            _lib.check(lib.sphrt_cg_curvature_f64(_lib.ptr(d), _lib.ptr(h), n_vox, c,
+                                                  _lib.ptr(part_php), _lib.stream_of(dev)),
+                       'sphrt_cg_curvature_f64')
+            return h
+
+        def update(h, rr_in, php_in, stop, rr_out):
+            _lib.check(lib.sphrt_cg_update_f64(
+                _lib.ptr(x), _lib.ptr(r), _lib.ptr(p), _lib.ptr(h), n_vox, _lib.ptr(rr_in),
+                _lib.ptr(php_in), pn, _lib.ptr(stop), _lib.ptr(rr_out), _lib.stream_of(dev)),
+                'sphrt_cg_update_f64')
+
+        # r_0 = -grad J(x0) and its partial sums: an update with alpha = 1 / 1 on r = p = 0
+        one = t.zeros(pn, dtype=f64, device=dev)
+        one[0] = 1.0
+        update(curvature(x, True), one, one, None, part_rr[0])
+        p.copy_(r)
+        stop = (_kernel_sum(part_rr[0]) * (tol * tol)).reshape(1) if tol > 0 else None
+        done = 0
+        try:
+            for it in bar:
+                h = curvature(p, False)
+                update(h, part_rr[it], part_php, stop, part_rr[it + 1])
+                _lib.check(lib.sphrt_cg_direction_f64(
+                    _lib.ptr(p), _lib.ptr(r), n_vox, _lib.ptr(part_rr[it + 1]),
+                    _lib.ptr(part_rr[it]), pn, _lib.ptr(stop), _lib.stream_of(dev)),
+                    'sphrt_cg_direction_f64')
+                done = it + 1
+        except KeyboardInterrupt:
+            pass
+        y_hat = f(x)       # (goes out before the readback waits)
+        sums = _kernel_sum(part_rr[:done + 1])
+        host = (t.cat([sums, stop]) if stop is not None else sums).cpu().tolist()
+    return x, y_hat, _cg_info(host[:done + 1], host[-1] if stop is not None else None)
