@@ -521,6 +521,26 @@ int sphrt_robust_residual_f64(const double *yhat, const void *y, int y_is_f64, i
                               int kind, double delta,
                               const double *ray_scale, const double *weight, const int32_t *order,
                               double *r_scaled, double *partial_sums, void *stream);
+/* The Poisson fidelity's tail (PoissonLoss: lam * mean(w * (p - y * log(p + eps))), torch's
+ * poisson_nll_loss(p, y, log_input=False, full=False, eps) under the mask): the grid, the use of
+ * `order`, the sphrt_loss_partials(n) partial sums and their fixed order are
+ * sphrt_robust_residual_f64's.  With i = order ? order[j] : j, p = yhat[i], s = ray_scale[i]:
+ *   q           = p + eps                             one rounding (a float32 y promoted exactly)
+ *   r_scaled[j] = s + ((-s) * y[i]) / q               a product, a quotient, a sum: three roundings
+ *   partial sums of weight[i] * (p - y[i] * log(q))   the device's log, then three roundings
+ * r_scaled[j] is the gradient autograd leaves at p for an incoming per-element gradient s —
+ * the sub, mul and log backward of ATen's composite input - target * log(input + eps), in that
+ * order — bitwise torch.autograd.grad's on the device, and the summed terms are bitwise torch's
+ * own elementwise ones (both tested on an MI355X, tests/test_gpu_poisson_gradient.py).  Every
+ * product is a plain multiply and the quotient a plain division, whatever -ffp-contract says.
+ * There are no guards: q of +-0 gives -+inf or NaN, a negative q a NaN log, and inf and NaN
+ * propagate, as in torch; denormals are not flushed.  Fails on the host, before any launch, on an
+ * eps that is not finite and > 0, on n <= 0 and on a null yhat, y, ray_scale, weight, r_scaled or
+ * partial_sums (`order` may be null). */
+int sphrt_poisson_residual_f64(const double *yhat, const void *y, int y_is_f64, int64_t n,
+                               double eps, const double *ray_scale, const double *weight,
+                               const int32_t *order, double *r_scaled, double *partial_sums,
+                               void *stream);
 int sphrt_neg_reg_f64(const double *d, int64_t n, double c_neg, double *g, double *partial_sums,
                       void *stream);
 /* SmoothRegularizer (loss.py; not in the reference): a difference penalty over the trailing axes
@@ -687,6 +707,30 @@ int sphrt_trace_normal_robust_f64(const sphrt_plan *plan, const sphrt_rays *rays
                                   double *yhat, int64_t y_chan_stride,
                                   double *acc, void *workspace, size_t workspace_size,
                                   void *stream);
+/* Poisson fidelity: sphrt_trace_normal_weighted_f64 with the Poisson weight in the scaled
+ * residual's place.  It is not a function of the residual: it is formed from the sum and the
+ * measurement separately, by sphrt_poisson_residual_f64's sequence:
+ *   yhat[c][i] = sum density[c][vox] * len          bitwise sphrt_trace_integrate_f64's
+ *   q          = yhat[c][i] + eps                   one rounding
+ *   w          = s + ((-s) * m[c][i]) / q           s = ray_scale[c][i]; three roundings
+ *   acc[c][vox] += w * len                          one more, then a float64 atomic
+ * so acc receives A^T(ray_scale .* (1 - m / (A density + eps))), the gradient of
+ * sum ray_scale .* (p - m log(p + eps)).  w is formed once per ray and channel (the lane-serial
+ * exact walk re-forms it per segment, as it re-reads the sum).  No guards: q <= 0, inf and NaN
+ * give what IEEE gives.  Channels, ray_chan_div, a miss (yhat = 0, nothing added) and the
+ * workspace as the robust entry's.  Refusals, all on the host before any launch: an eps that is
+ * not finite and > 0, then sphrt_trace_normal_weighted_f64's.
+ * There is no fixed-point form: its bound needs max|w|, and |1 - m / (p + eps)| has no bound
+ * before the forward has run.  The deterministic gradient is two traces over existing entries:
+ * sphrt_trace_integrate_f64, sphrt_poisson_residual_f64, sphrt_fixed_scale_f64(a = r_scaled,
+ * fa = L), sphrt_trace_backproject_fixed_f64, sphrt_fixed_finalize_f64. */
+int sphrt_trace_normal_poisson_f64(const sphrt_plan *plan, const sphrt_rays *rays,
+                                   const double *density, const double *m,
+                                   const double *ray_scale, double eps,
+                                   int64_t n_chan, int64_t chan_stride, int64_t ray_chan_div,
+                                   double *yhat, int64_t y_chan_stride,
+                                   double *acc, void *workspace, size_t workspace_size,
+                                   void *stream);
 
 /* ---- deterministic no-store adjoint: fixed-point scatter (csrc/fixed.hpp) --------------------
  * The two entries above sum y * len with float64 atomics, so their results differ in the last

@@ -130,6 +130,8 @@ _SIGNATURES = [
                                        c_vp]),
     ('sphrt_robust_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_vp, c_vp, c_vp,
                                           c_vp, c_vp, c_vp]),
+    ('sphrt_poisson_residual_f64', c_int, [c_vp, c_vp, c_int, c_i64, c_dbl, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp]),
     ('sphrt_neg_reg_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_vp, c_vp]),
     ('sphrt_smooth_reg_f64', c_int, [c_vp, c_i64, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl,
                                      c_dbl, c_int, c_dbl, c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp,
@@ -158,6 +160,9 @@ _SIGNATURES = [
     ('sphrt_trace_normal_robust_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_vp,
                                               c_int, c_dbl, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp,
                                               c_vp, ctypes.c_size_t, c_vp]),
+    ('sphrt_trace_normal_poisson_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_vp, c_vp,
+                                               c_dbl, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                               ctypes.c_size_t, c_vp]),
     ('sphrt_fixed_scale_f64', c_int, [c_vp, c_i64, c_dbl, c_vp, c_i64, c_dbl, c_vp, c_vp]),
     ('sphrt_trace_backproject_fixed_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_i64,
                                                   c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,

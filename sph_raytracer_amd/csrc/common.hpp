@@ -84,6 +84,25 @@ inline int refuse_robust(int kind, double delta, double& rd) {
     return 0;
 }
 
+// The Poisson fidelity (PoissonLoss: p - y * log(p + eps), torch's poisson_nll_loss with
+// log_input=False), shared by the trace's sink and the loss tail.  q = p + eps, one rounding.
+// poisson_weight: the gradient autograd leaves at p for an incoming gradient s — the sub, mul
+// and log backward of ATen's composite input - target * log(input + eps): s + ((-s) * y) / q.
+// Plain multiplies and a plain division, whatever -ffp-contract says; no guards: q <= 0, inf and
+// NaN give what IEEE gives, as in torch.
+__device__ __forceinline__ double poisson_weight(double q, double y, double s) {
+#pragma clang fp contract(off)
+    const double t = (-s) * y;
+    const double u = t / q;
+    return s + u;
+}
+// The Poisson entries' own host refusal: an eps that is not finite and > 0.
+inline int refuse_poisson(double eps) {
+    if (!(eps > 0.0) || __builtin_isinf(eps))       // (a NaN fails the compare)
+        return fail("the Poisson eps must be finite and > 0, not %g", eps);
+    return 0;
+}
+
 // Validate plan + batch and convert to the by-value kernel argument forms.
 inline int resolve(const sphrt_plan* plan, const sphrt_rays* rays, GridDev& G, RaysDev& R,
                    void* stream) {

@@ -103,6 +103,33 @@ __global__ __launch_bounds__(kLossThreads) void robust_residual_kernel(
     block_partial(acc, part);
 }
 
+// The Poisson tail (PoissonLoss: lam * mean(w * (p - y * log(p + eps)))): with p = yhat[i] and
+// q = p + eps (one rounding), r_scaled[j] = ray_scale[i] + ((-ray_scale[i]) * y[i]) / q
+// (poisson_weight, common.hpp: autograd's gradient at p for an incoming ray_scale[i]) and partial
+// sums of weight[i] * (p - y[i] * log(q)) — torch's poisson_nll_loss forward under the mask,
+// operation by operation, the device's log.  No guards: q <= 0 gives NaN or -+inf as in torch.
+// The same grid, strides and tree.
+template <typename TY>
+__global__ __launch_bounds__(kLossThreads) void poisson_residual_kernel(
+    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n, double eps,
+    const double* __restrict__ ray_scale, const double* __restrict__ weight,
+    const int32_t* __restrict__ order, double* __restrict__ r_scaled, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
+         j += (int64_t)gridDim.x * kLossThreads) {
+        const int64_t i = order ? (int64_t)order[j] : j;
+        const double p = yhat[i], m = (double)y[i];
+        const double q = p + eps;
+        r_scaled[j] = poisson_weight(q, m, ray_scale[i]);
+        const double t = m * log(q);
+        const double h = p - t;
+        const double wh = weight[i] * h;
+        acc += wh;
+    }
+    block_partial(acc, part);
+}
+
 // g -= c_neg where d < 0 (g.sub_(d.lt(0), alpha=c): g - c * 0 is g itself, signed zeros
 // included); partial sums of |clamp(d, max=0)| (NaN stays NaN).
 __global__ __launch_bounds__(kLossThreads) void neg_reg_kernel(
@@ -485,6 +512,27 @@ extern "C" int sphrt_robust_residual_f64(const double* yhat, const void* y, int 
                            0, st, yhat, (const float*)y, n, rd, ray_scale, weight, order, r_scaled,
                            partial_sums);
     return check_launch("robust_residual");
+}
+
+extern "C" int sphrt_poisson_residual_f64(const double* yhat, const void* y, int y_is_f64,
+                                          int64_t n, double eps, const double* ray_scale,
+                                          const double* weight, const int32_t* order,
+                                          double* r_scaled, double* partial_sums, void* stream) {
+    if (int e = refuse_poisson(eps)) return e;
+    if (n <= 0) return fail("sphrt_poisson_residual_f64: empty measurement");
+    if (!yhat || !y || !ray_scale || !weight || !r_scaled || !partial_sums)
+        return fail("null buffer");
+    StreamGuard guard(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (y_is_f64)
+        hipLaunchKernelGGL(poisson_residual_kernel<double>, dim3(loss_grid(n)), dim3(kLossThreads),
+                           0, st, yhat, (const double*)y, n, eps, ray_scale, weight, order,
+                           r_scaled, partial_sums);
+    else
+        hipLaunchKernelGGL(poisson_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads),
+                           0, st, yhat, (const float*)y, n, eps, ray_scale, weight, order, r_scaled,
+                           partial_sums);
+    return check_launch("poisson_residual");
 }
 
 extern "C" int sphrt_neg_reg_f64(const double* d, int64_t n, double c_neg, double* g,

@@ -54,14 +54,19 @@ namespace sphrt {
 // for the one lane that streams a sorted list from the workspace.
 enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_INTEGRATE = 2, MODE_EMIT = 3, MODE_BOUND = 4,
        MODE_SCATTER = 5, MODE_NORMAL = 6, MODE_SCATTER_FIXED = 7, MODE_NORMAL_FIXED = 8,
-       MODE_NORMAL_W = 9, MODE_NORMAL_W_FIXED = 10, MODE_NORMAL_R = 11, MODE_NORMAL_R_FIXED = 12 };
+       MODE_NORMAL_W = 9, MODE_NORMAL_W_FIXED = 10, MODE_NORMAL_R = 11, MODE_NORMAL_R_FIXED = 12,
+       MODE_NORMAL_P = 13 };
 constexpr bool mode_scatter(int m) { return m == MODE_SCATTER || m == MODE_SCATTER_FIXED; }
 // (the weighted normal modes: the residual's factor per ray and channel, TraceOut::ray_scale)
 // (the robust normal modes: the weighted ones with psi of the residual in the residual's place,
 // robust_psi; TraceOut::robust_delta picks psi)
 constexpr bool mode_robust(int m) { return m == MODE_NORMAL_R || m == MODE_NORMAL_R_FIXED; }
+// (the Poisson normal mode: the weighted one with the weight formed from the sum and the
+// measurement separately, poisson_weight; TraceOut::poisson_eps.  No fixed form: |w| has no bound
+// before the forward has run)
+constexpr bool mode_poisson(int m) { return m == MODE_NORMAL_P; }
 constexpr bool mode_weighted(int m) {
-    return m == MODE_NORMAL_W || m == MODE_NORMAL_W_FIXED || mode_robust(m);
+    return m == MODE_NORMAL_W || m == MODE_NORMAL_W_FIXED || mode_robust(m) || mode_poisson(m);
 }
 constexpr bool mode_normal(int m) {
     return m == MODE_NORMAL || m == MODE_NORMAL_FIXED || mode_weighted(m);
@@ -442,9 +447,10 @@ struct TraceOut {
     int32_t* counts;          // COUNT
     const int64_t* row_ptr;   // FILL
     int32_t* vox;
-    union {                   // one slot (FILL / EMIT and NORMAL_R* never meet): TraceOut keeps its
-        double* len;              // size, and the kernel arguments of the other modes their place
-        double robust_delta;      // NORMAL_R*: Huber's delta (> 0), or 0 for the sign (ABS)
+    union {                   // one slot (FILL / EMIT, NORMAL_R* and NORMAL_P never meet): TraceOut
+        double* len;              // keeps its size, and the kernel arguments of the other modes
+        double robust_delta;      // their place.  NORMAL_R*: Huber's delta (> 0), or 0 for the
+        double poisson_eps;       // sign (ABS); NORMAL_P: the eps of p + eps (> 0)
     };
     const T* density;         // INTEGRATE; SCATTER: y, its channels out_chan_stride apart
     int64_t n_chan, chan_stride, ray_chan_div;
@@ -540,13 +546,21 @@ __device__ __forceinline__ double residual_factor(const TraceOut<T>& o, int64_t 
     else return o.scale;
 }
 
-// NORMAL: what the scatter weighs a ray's lengths with, from the residual r = sum - m of the
-// per-ray element rc: r * factor (two roundings with r's), or (NORMAL_R*) psi(r) * ray_scale[rc]
-// (robust_psi, common.hpp; robust_delta is wave-uniform: one scalar branch).
+// NORMAL: what the scatter weighs a ray's lengths with, from the sum and the measurement m of
+// the per-ray element rc.  With the residual r = sum - m: r * factor (two roundings with r's), or
+// (NORMAL_R*) psi(r) * ray_scale[rc] (robust_psi, common.hpp; robust_delta is wave-uniform: one
+// scalar branch).  NORMAL_P forms no residual: with q = sum + eps,
+// ray_scale[rc] + ((-ray_scale[rc]) * m) / q (poisson_weight, common.hpp).
 template <int MODE, typename T>
-__device__ __forceinline__ double residual_weight(const TraceOut<T>& o, int64_t rc, double r) {
-    if constexpr (mode_robust(MODE)) return robust_psi(r, o.robust_delta) * o.ray_scale[rc];
-    else return r * residual_factor<MODE>(o, rc);
+__device__ __forceinline__ double residual_weight(const TraceOut<T>& o, int64_t rc, double sum,
+                                                  double m) {
+    if constexpr (mode_poisson(MODE)) {
+        return poisson_weight(sum + o.poisson_eps, m, o.ray_scale[rc]);
+    } else {
+        const double r = sum - m;
+        if constexpr (mode_robust(MODE)) return robust_psi(r, o.robust_delta) * o.ray_scale[rc];
+        else return r * residual_factor<MODE>(o, rc);
+    }
 }
 
 // The segment sink: what every wave-level path does with a ray's list once it is compacted —
@@ -562,7 +576,8 @@ __device__ __forceinline__ double residual_weight(const TraceOut<T>& o, int64_t 
 //                every lane; two roundings, sphrt_sq_residual_f64's; NORMAL_W*: scale is
 //                ray_scale[rc], one wave-uniform load per ray and channel, residual_factor;
 //                NORMAL_R*: psi(sum - m) * ray_scale[rc], psi once per ray and channel,
-//                residual_weight).
+//                residual_weight; NORMAL_P: the Poisson weight of (sum, m, ray_scale[rc], eps),
+//                once per ray and channel too).
 template <int MODE, typename T>
 __device__ __forceinline__ void consume_list(const TraceOut<T>& o, int64_t ray, int lane, int nseg,
                                              const int32_t* seg_vox, const double* seg_len,
@@ -597,7 +612,7 @@ __device__ __forceinline__ void consume_list(const TraceOut<T>& o, int64_t ray, 
                 for (int q = lane; q < nseg; q += 64) sum += (double)rho[seg_vox[q]] * seg_len[q];
                 sum = wave_sum(sum);
                 if (lane == 0) o.out[rc] = (T)sum;
-                if constexpr (kScatter) w = residual_weight<MODE>(o, rc, sum - o.meas[rc]);
+                if constexpr (kScatter) w = residual_weight<MODE>(o, rc, sum, o.meas[rc]);
             } else {
                 w = (double)o.density[rc];
             }
@@ -1580,7 +1595,7 @@ __device__ void exact_walk(const GridDev& G, const TraceOut<T>& o, int64_t ray, 
                     const int64_t rc = ray_index(o, c, ray);
                     double w;                                  // the residual, or y
                     if constexpr (mode_normal(MODE))
-                        w = residual_weight<MODE>(o, rc, (double)o.out[rc] - o.meas[rc]);
+                        w = residual_weight<MODE>(o, rc, (double)o.out[rc], o.meas[rc]);
                     else
                         w = (double)o.density[rc];
                     acc_add<MODE>(o.acc, c * o.chan_stride + vx, w * len, fx);
@@ -2365,7 +2380,8 @@ static TraceOut<T> fused_out(const T* in, int64_t n_chan, int64_t chan_stride, i
     if (ray_scale) o.ray_scale = ray_scale;
     else o.scale = scale;
     o.fixed_rec = static_cast<const int32_t*>(scale_rec);
-    if (robust_delta != 0.0) o.robust_delta = robust_delta;   // (shares len's slot: null here)
+    // (shares len's slot, null here; NORMAL_P: the same slot holds eps, poisson_eps)
+    if (robust_delta != 0.0) o.robust_delta = robust_delta;
     return o;
 }
 static const char* refuse_channels(int64_t n_chan, int64_t ray_chan_div) {
@@ -2476,7 +2492,8 @@ static int run_backproject(const sphrt_plan* plan, const sphrt_rays* rays, const
                            workspace, workspace_size, stream);
 }
 // (NORMAL_W*, NORMAL_R*: the residual's factor is ray_scale, laid out as m, and `scale` is unused;
-// NORMAL_R*: robust_delta is TraceOut's, the entry's refusals of kind and delta made already)
+// NORMAL_R*: robust_delta is TraceOut's, the entry's refusals of kind and delta made already;
+// NORMAL_P: eps travels in robust_delta's place)
 template <int MODE>
 static int run_normal(const sphrt_plan* plan, const sphrt_rays* rays, const double* density,
                       const double* m, double scale, const double* ray_scale, int64_t n_chan,
@@ -2588,6 +2605,22 @@ extern "C" int sphrt_trace_normal_robust_fixed_f64(
     return run_normal<MODE_NORMAL_R_FIXED>(plan, rays, density, m, 0.0, ray_scale, n_chan,
                                            chan_stride, ray_chan_div, yhat, y_chan_stride, acc,
                                            scale_rec, workspace, workspace_size, stream, rd);
+}
+
+// The Poisson entry: refuse_poisson (common.hpp) first, then the weighted entries' path.  There is
+// no fixed-point form (mode_poisson): the deterministic gradient is two traces over
+// sphrt_trace_integrate_f64 and sphrt_trace_backproject_fixed_f64.
+extern "C" int sphrt_trace_normal_poisson_f64(const sphrt_plan* plan, const sphrt_rays* rays,
+                                              const double* density, const double* m,
+                                              const double* ray_scale, double eps, int64_t n_chan,
+                                              int64_t chan_stride, int64_t ray_chan_div,
+                                              double* yhat, int64_t y_chan_stride, double* acc,
+                                              void* workspace, size_t workspace_size,
+                                              void* stream) {
+    if (int e = refuse_poisson(eps)) return e;
+    return run_normal<MODE_NORMAL_P>(plan, rays, density, m, 0.0, ray_scale, n_chan, chan_stride,
+                                     ray_chan_div, yhat, y_chan_stride, acc, nullptr, workspace,
+                                     workspace_size, stream, eps);
 }
 
 template <typename F>

@@ -157,12 +157,13 @@ class ShardedOperator:
 
 def _declined(loss_fns):
     """Does gd() keep these terms out of its direct loop, whatever retrieval._direct_plan takes
-    on one GPU: a tensor projection_mask, a robust fidelity term (AbsLoss, HuberLoss) or a
-    SmoothRegularizer — only the unmasked SquareLoss loop with a NegRegularizer is worked out
+    on one GPU: a tensor projection_mask, a robust fidelity term (AbsLoss, HuberLoss), a
+    PoissonLoss or a SmoothRegularizer — only the unmasked SquareLoss loop with a NegRegularizer is worked out
     over ranks."""
-    from .loss import AbsLoss, HuberLoss, SmoothRegularizer
+    from .loss import AbsLoss, HuberLoss, PoissonLoss, SmoothRegularizer
     return any(isinstance(fn.projection_mask, tr.Tensor)
-               or type(fn) in (AbsLoss, HuberLoss, SmoothRegularizer) for fn in loss_fns)
+               or type(fn) in (AbsLoss, HuberLoss, PoissonLoss, SmoothRegularizer)
+               for fn in loss_fns)
 
 
 def gd(f, y_local, model, coeffs=None, num_iterations=100, loss_fns=None, optim=tr.optim.Adam,

@@ -105,6 +105,31 @@ class HuberLoss(Loss):
             pred, y, reduction='none', delta=self.delta)))
 
 
+class PoissonLoss(Loss):
+    """mean(p - y log(p + eps)), p = f(d): the Poisson negative log-likelihood of photon counts y
+    (up to the term in y alone), the fidelity for low counts — torch's ``poisson_nll_loss(p, y,
+    log_input=False, full=False, eps=eps)`` under the mask and the mean.  Not in the reference.
+    No guards: where p + eps <= 0 the log and the quotient give what torch gives (NaN, +-inf),
+    and they propagate.  A float32 y against a float64 forward is promoted, as HuberLoss does."""
+    kind = 'fidelity'
+
+    def __init__(self, eps=1e-8, **kwargs):
+        # (a real number — int, float, a numpy scalar; no bool, no tensor — finite and > 0)
+        if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not eps > 0 \
+                or eps == float('inf'):
+            raise ValueError(f'PoissonLoss needs a finite eps > 0, not {eps!r}')
+        self.eps = float(eps)
+        super().__init__(**kwargs)
+
+    def compute(self, f, y, d, c):
+        pred = f(_scaled(self.volume_mask, d))
+        if y.dtype != pred.dtype:
+            dt = t.promote_types(y.dtype, pred.dtype)
+            y, pred = y.to(dt), pred.to(dt)
+        return t.mean(_scaled(self.projection_mask, t.nn.functional.poisson_nll_loss(
+            pred, y, log_input=False, full=False, eps=self.eps, reduction='none')))
+
+
 class CheaterLoss(Loss):
     """L2 distance to a known ground-truth density (monitoring only)."""
     kind = 'oracle'

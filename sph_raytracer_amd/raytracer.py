@@ -1178,7 +1178,7 @@ def _robust_args(loss, delta):
     number (`_real_delta`: a Python or numpy scalar; a tensor is refused, reading it could
     sync)."""
     if not isinstance(loss, str) or loss not in ('square', 'abs', 'huber'):
-        raise ValueError(f"loss must be 'square', 'abs' or 'huber', not {loss!r}")
+        raise ValueError(f"loss must be 'square', 'abs' or 'huber', or 'poisson', not {loss!r}")
     if loss == 'huber':
         if not _real_delta(delta):
             raise ValueError(f"loss='huber' needs a finite delta > 0, not {delta!r}")
@@ -1247,6 +1247,102 @@ def _fused_robust_gradient(parts, grid, density, m, scale, dev, robust, determin
     else:
         acc, fixed = tr.zeros(d.numel(), dtype=tr.float64, device=dev), None
     _launch_normal_robust(parts, grid, d, mv, rs, robust, n_chan, div, yhat, acc, dev, fixed)
+    rdt, rdev = density.dtype, density.device
+    return (_from_f64(yhat, rdt, dev).reshape(out_shape).to(rdev),
+            _from_f64(acc, rdt, dev).reshape(density.shape).to(rdev))
+
+
+POISSON_EPS = 1e-8      # torch.nn.functional.poisson_nll_loss's default
+
+
+def _poisson_args(loss, delta, eps):
+    """-> the eps of loss='poisson' as the C entries take it (None given: POISSON_EPS), or None
+    for any other `loss` (which `_robust_args` then judges).  ValueError on a delta given to
+    'poisson', an eps given to anything else, and an eps that is not a real number (`_real_delta`'s
+    rule: no bool, no tensor), finite and > 0 (host only)."""
+    if not (isinstance(loss, str) and loss == 'poisson'):
+        if eps is not None:
+            raise ValueError(f"eps belongs to loss='poisson', not loss={loss!r}")
+        return None
+    if delta is not None:
+        raise ValueError("delta belongs to loss='huber', not loss='poisson'")
+    if eps is None:
+        return POISSON_EPS
+    if not _real_delta(eps):
+        raise ValueError(f"loss='poisson' needs a finite eps > 0, not {eps!r}")
+    return float(eps)
+
+
+def _launch_normal_poisson(parts, grid, d, m, rs, eps, n_chan, div, yhat, acc, dev):
+    """_launch_normal's Poisson form, sphrt_trace_normal_poisson_f64: yhat receives A d and the
+    zeroed acc gains A^T(rs + ((-rs) m) / (A d + eps)), rs the flat float64 factor per
+    measurement on `dev`.  Float64 atomics only: there is no fixed-point form."""
+    plan, batch, ws = parts
+    if rs.numel() != m.numel():
+        raise ValueError(f'{rs.numel()} ray factors for {m.numel()} measurements')
+    _lib.check(_lib.load().sphrt_trace_normal_poisson_f64(
+        plan.handle, batch.desc, _lib.ptr(d), _lib.ptr(m), _lib.ptr(rs), eps, n_chan,
+        math.prod(grid.shape[-3:]), div, _lib.ptr(yhat), batch.n, _lib.ptr(acc), _lib.ptr(ws),
+        ws.numel(), _lib.stream_of(dev)), 'sphrt_trace_normal_poisson_f64')
+
+
+def _poisson_two_trace(parts, grid, d, m, rs, eps, n_chan, div, yhat, acc, dev, fixed):
+    """The deterministic Poisson gradient, two traces over existing entries: the forward into
+    yhat (sphrt_trace_integrate_f64), the Poisson weight of every measurement
+    (sphrt_poisson_residual_f64: rs + ((-rs) m) / (yhat + eps)), the scale of max|weight| L, the
+    fixed-point back-projection into the zeroed integer accumulator `fixed` and its values into
+    acc — MatrixFreeOperator.T's own deterministic sequence on that weight, so the same bits.
+    (The residual launch's loss partial sums are not used here: its `weight` is rs.)"""
+    plan, batch, ws = parts
+    if rs.numel() != m.numel():
+        raise ValueError(f'{rs.numel()} ray factors for {m.numel()} measurements')
+    lib, stream = _lib.load(), _lib.stream_of(dev)
+    vol = math.prod(grid.shape[-3:])
+    _lib.check(lib.sphrt_trace_integrate_f64(plan.handle, batch.desc, _lib.ptr(d), n_chan, vol,
+                                             div, _lib.ptr(yhat), batch.n, _lib.ptr(ws),
+                                             ws.numel(), stream), 'sphrt_trace_integrate')
+    psi = tr.empty_like(yhat)
+    part = tr.empty(lib.sphrt_loss_partials(yhat.numel()), dtype=tr.float64, device=dev)
+    _lib.check(lib.sphrt_poisson_residual_f64(
+        _lib.ptr(yhat), _lib.ptr(m), 1, yhat.numel(), eps, _lib.ptr(rs), _lib.ptr(rs), None,
+        _lib.ptr(psi), _lib.ptr(part), stream), 'sphrt_poisson_residual_f64')
+    _poisson_backproject_fixed(parts, grid, psi, n_chan, div, acc, dev, fixed)
+
+
+def _poisson_backproject_fixed(parts, grid, psi, n_chan, div, acc, dev, fixed):
+    """_fused_adjoint's deterministic sequence into the caller's buffers: the scale record of
+    max|psi| L, sphrt_trace_backproject_fixed_f64 into the zeroed fixed[0], its values into acc."""
+    plan, batch, ws = parts
+    lib, stream = _lib.load(), _lib.stream_of(dev)
+    _lib.check(lib.sphrt_fixed_scale_f64(_lib.ptr(psi), psi.numel(), _outer_diameter(grid), None,
+                                         0, 0.0, _lib.ptr(fixed[1]), stream),
+               'sphrt_fixed_scale_f64')
+    _lib.check(lib.sphrt_trace_backproject_fixed_f64(
+        plan.handle, batch.desc, _lib.ptr(psi), n_chan, batch.n, div, _lib.ptr(fixed[0]),
+        math.prod(grid.shape[-3:]), _lib.ptr(fixed[1]), _lib.ptr(ws), ws.numel(), stream),
+        'sphrt_trace_backproject_fixed_f64')
+    _fixed_finalize(fixed, acc, dev)
+
+
+def _fused_poisson_gradient(parts, grid, density, m, scale, dev, eps, deterministic=False,
+                            weights=None):
+    """_fused_robust_gradient for the Poisson fidelity: (A density, A^T(ray_scale (1 - m /
+    (A density + eps)))), ray_scale = weights * scale per measurement (_ray_scale), or `scale`
+    expanded once — from one trace, or with `deterministic` from two (_poisson_two_trace)."""
+    n_chan, div, out_shape = _gradient_layout(grid, parts[1].shape, density.shape, m.shape)
+    d, mv = _to_f64(density, dev), _to_f64(m, dev)
+    if weights is None:
+        rs = tr.full((mv.numel(),), float(scale), dtype=tr.float64, device=dev)
+    else:
+        rs, _ = _ray_scale(weights, scale, m.shape, dev, False)
+    yhat = tr.empty(mv.numel(), dtype=tr.float64, device=dev)
+    if deterministic:
+        acc = tr.empty(d.numel(), dtype=tr.float64, device=dev)
+        _poisson_two_trace(parts, grid, d, mv, rs, eps, n_chan, div, yhat, acc, dev,
+                           _fixed_buffers(d.numel(), dev))
+    else:
+        acc = tr.zeros(d.numel(), dtype=tr.float64, device=dev)
+        _launch_normal_poisson(parts, grid, d, mv, rs, eps, n_chan, div, yhat, acc, dev)
     rdt, rdev = density.dtype, density.device
     return (_from_f64(yhat, rdt, dev).reshape(out_shape).to(rdev),
             _from_f64(acc, rdt, dev).reshape(density.shape).to(rdev))
@@ -2277,7 +2373,8 @@ class MatrixFreeOperator:
     mask, noise weights) ``op.T(w * scale * (op(density) - m))``, still from one trace, and gd()
     over a ``SquareLoss(projection_mask=w)`` runs its direct loop on that call; with
     ``loss='abs'`` or ``loss='huber', delta=d`` the residual is replaced by its sign or its clamp
-    to +-d (gd() over an ``AbsLoss`` or a ``HuberLoss``).  There are
+    to +-d (gd() over an ``AbsLoss`` or a ``HuberLoss``), and with ``loss='poisson'`` by the
+    Poisson likelihood's ``1 - m / (op(density) + eps)`` (gd() over a ``PoissonLoss``).  There are
     no ``regs`` / ``lens`` / ``segments`` views: nothing is stored to show.  The workspace is
     shared by the calls: use an operator from one stream at a time."""
 
@@ -2334,7 +2431,7 @@ class MatrixFreeOperator:
         return self._apply_adjoint(y, dshape, y.dtype, self._rdev)
 
     def residual_gradient(self, density, measurements, scale=1.0, weights=None, loss='square',
-                          delta=None):
+                          delta=None, eps=None):
         """-> (yhat, grad) from one trace (sphrt_trace_normal_f64): ``yhat = op(density)`` and
         ``grad = A^T(scale * (yhat - measurements))``, the gradient in ``density`` of
         ``0.5 * scale * ((op(density) - measurements) ** 2).sum()`` — what ``op`` followed by
@@ -2362,6 +2459,17 @@ class MatrixFreeOperator:
         a factor that is not finite then gives NaN everywhere.  ``loss='square'`` is the call
         above, unchanged.
 
+        ``loss='poisson'`` is the Poisson negative log-likelihood of photon counts,
+        ``scale * (weights * (p - measurements * log(p + eps))).sum()`` with ``p = op(density)``
+        (torch's ``poisson_nll_loss``, ``log_input=False``): ``grad = A^T(ray_scale * (1 -
+        measurements / (yhat + eps)))``, formed as autograd forms it, ``ray_scale + ((-ray_scale) *
+        measurements) / (yhat + eps)``, from one trace (sphrt_trace_normal_poisson_f64).  ``eps``
+        (default 1e-8, finite and > 0) belongs to this loss alone and ``delta`` is refused with
+        it.  There are no guards: where ``yhat + eps <= 0`` the quotient is what IEEE gives.  The
+        weight has no bound before the forward has run, so with ``op.deterministic`` the call
+        costs two traces, not one — the forward, the weights, then the fixed-point back-projection
+        ``op.T`` itself runs: the same bits as ``op(density)`` followed by ``op.T`` of that weight.
+
         ``measurements`` has ``op(density)``'s shape.  Static grids take leading channel axes; a
         dynamic grid pairs time slices with views as the forward does, so ``grad`` is autograd's
         gradient of the dynamic forward.  Computed in float64 (``yhat`` is bitwise the float64
@@ -2371,7 +2479,8 @@ class MatrixFreeOperator:
         device.  Not differentiable."""
         density, m = tr.as_tensor(density), tr.as_tensor(measurements)
         _gradient_layout(self.grid, self._ray_shape, density.shape, m.shape)   # (host only)
-        robust = _robust_args(loss, delta)                                      # (host only)
+        p_eps = _poisson_args(loss, delta, eps)                                 # (host only)
+        robust = _robust_args(loss, delta) if p_eps is None else None           # (host only)
         if weights is not None:
             weights = tr.as_tensor(weights)
             if weights.dtype not in (tr.bool, tr.float32, tr.float64):
@@ -2384,6 +2493,10 @@ class MatrixFreeOperator:
                 raise ValueError(f'weights of shape {tuple(weights.shape)} do not broadcast to '
                                  f'the measurements {tuple(m.shape)}')
         with tr.cuda.device(self._cdev):
+            if p_eps is not None:
+                return _fused_poisson_gradient(self._parts, self.grid, density, m, scale,
+                                               self._cdev, p_eps, bool(self.deterministic),
+                                               weights)
             if robust is not None:
                 return _fused_robust_gradient(self._parts, self.grid, density, m, scale,
                                               self._cdev, robust, bool(self.deterministic),
@@ -2429,6 +2542,28 @@ class MatrixFreeOperator:
             fixed = None
         _launch_normal_robust(self._parts, self.grid, d, m, rs, robust, 1, 0, yhat, acc,
                               self._cdev, fixed, scaled)
+
+    def _poisson_into(self, d, m, rs, eps, yhat, acc):
+        """_normal_into for the Poisson fidelity, atomic mode: `rs` the flat float64 factor per
+        measurement; yhat receives A d and the zeroed acc gains A^T(rs (1 - m / (A d + eps)))
+        from one trace.  (The deterministic loop runs _forward_into, the residual kernel and
+        _backproject_fixed_into: two traces.)"""
+        _launch_normal_poisson(self._parts, self.grid, d, m, rs, eps, 1, 0, yhat, acc, self._cdev)
+
+    def _forward_into(self, d, yhat):
+        """A d into the caller's flat float64 yhat (sphrt_trace_integrate_f64): bitwise op(d)."""
+        plan, batch, ws = self._parts
+        _lib.check(_lib.load().sphrt_trace_integrate_f64(
+            plan.handle, batch.desc, _lib.ptr(d), 1, math.prod(self.grid.shape[-3:]), 0,
+            _lib.ptr(yhat), batch.n, _lib.ptr(ws), ws.numel(), _lib.stream_of(self._cdev)),
+            'sphrt_trace_integrate')
+
+    def _backproject_fixed_into(self, y, acc, fixed):
+        """op.T(y)'s deterministic sequence into the caller's acc through the caller's `fixed`
+        (_fixed_buffers(), zeroed here): the scale of max|y| L, the fixed-point back-projection,
+        its values — the bits of op.T(y) with `deterministic` set; nothing allocated."""
+        fixed[0].zero_()
+        _poisson_backproject_fixed(self._parts, self.grid, y, 1, 0, acc, self._cdev, fixed)
 
     def __repr__(self):
         if self.dynamic:

@@ -14,7 +14,8 @@ import math
 
 import torch as t
 
-from .loss import AbsLoss, HuberLoss, NegRegularizer, SmoothRegularizer, SquareLoss
+from .loss import (AbsLoss, HuberLoss, NegRegularizer, PoissonLoss, SmoothRegularizer,
+                   SquareLoss)
 from .model import FullyDenseModel
 
 try:
@@ -129,8 +130,8 @@ def _unit(m):
 def _direct_plan(f, y, model, coeffs, loss_fns, optim_vars):
     """The loss terms of a loop `_gd_direct` runs without autograd, or None.  It covers the
     examples/static_retrieval.py loop: a FullyDenseModel (the coefficients are the density) on a
-    static Operator, one fidelity term — a SquareLoss, an AbsLoss or a HuberLoss, exactly those
-    types — at most one NegRegularizer and at most one SmoothRegularizer, scalar weights, no
+    static Operator, one fidelity term — a SquareLoss, an AbsLoss, a HuberLoss or a PoissonLoss,
+    exactly those types — at most one NegRegularizer and at most one SmoothRegularizer, scalar weights, no
     masks but the fidelity term's projection_mask (`_ray_mask`: per-ray weights, a mask of bad
     pixels), the coefficients the only optimised variable.  With all three terms the fidelity
     term must come first in `loss_fns`: autograd accumulates the terms [t1, t2, t3] of the total
@@ -167,7 +168,8 @@ def _ray_mask(mask, y):
         return False
 
 
-_FIDELITY = (SquareLoss, AbsLoss, HuberLoss)    # the direct loops' fidelity terms, by exact type
+# the direct loops' fidelity terms, by exact type
+_FIDELITY = (SquareLoss, AbsLoss, HuberLoss, PoissonLoss)
 
 
 def _robust_of(fid):
@@ -180,11 +182,16 @@ def _robust_of(fid):
     return None
 
 
+def _poisson_of(fid):
+    """The eps of a PoissonLoss as the C entries take it, None for any other fidelity term."""
+    return float(fid.eps) if type(fid) is PoissonLoss else None
+
+
 def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
     """(fidelity term, NegRegularizer or None) when model, variables, measurements and loss terms
     are those `_gd_direct` runs over the operator `f`, else None; with a SmoothRegularizer among
     the terms, the 3-tuple (fidelity, NegRegularizer or None, SmoothRegularizer).  The fidelity
-    term is exactly one SquareLoss, AbsLoss or HuberLoss (`_FIDELITY`; a subclass may compute
+    term is exactly one SquareLoss, AbsLoss, HuberLoss or PoissonLoss (`_FIDELITY`; a subclass may compute
     anything: the autograd loop); with both regularisers it is the first term (`_direct_plan`)."""
     if type(model) is not FullyDenseModel or hasattr(model, 'proj'):
         return None
@@ -250,6 +257,14 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     the adjoint's input is s * psi(f(d) - y) (sphrt_robust_residual_f64, which also sums
     w * |r| or w * huber(r); fused: sphrt_trace_normal_robust_f64 with ray_scale = s).  A NaN
     residual has a zero gradient under AbsLoss and a NaN one under HuberLoss, as in torch.
+    PoissonLoss, lam * mean(w * (p - y * log(p + eps))) with p = f(d): s = (lam / N) * w_i as
+    above, and the composite's sub, mul and log backward leave s + ((-s) * y) / (p + eps) at p —
+    not a function of the residual (sphrt_poisson_residual_f64, which also sums
+    w * (p - y * log(p + eps)); fused: sphrt_trace_normal_poisson_f64 with ray_scale = s).  That
+    weight has no bound before the forward has run, so a deterministic MatrixFreeOperator runs
+    two traces per iteration — the forward, the residual kernel, then op.T's own fixed-point
+    back-projection — where the other terms run one; the iterates are then bitwise the autograd
+    loop's over the same operator.
     Gradient of lam * mean(|clip(d, max=0)|): -(lam / N) where d < 0, else 0 (sign(0) = 0).
     The two are summed (IEEE addition commutes, so the order autograd accumulates them in does
     not matter) and handed to the optimiser as coeffs.grad.
@@ -309,9 +324,12 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     # a projection_mask: the loss's weights w and the residual's factors s, once, laid out as the
     # residual kernel reads y (in trace order where y was permuted above)
     w_res = s_res = weighted = None
-    robust = _robust_of(sq)
-    if robust is not None:
-        # a robust term's factors are always arrays (a unit mask: ones, and lam / N itself)
+    robust, poisson = _robust_of(sq), _poisson_of(sq)
+    # (a deterministic Poisson loop: two traces, the stored loop's order of launches)
+    two_trace = poisson is not None and fused and bool(f.deterministic)
+    if robust is not None or poisson is not None:
+        # a robust or Poisson term's factors are always arrays (a unit mask: ones, and lam / N
+        # itself)
         if isinstance(sq.projection_mask, t.Tensor):
             w_res = sq.projection_mask.detach().to(t.float64).expand(yd.shape).contiguous() \
                 .reshape(-1)
@@ -363,8 +381,13 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 if fused:
                     # f(d) into yhat_buf and A^T((f(d) - y) * (2 lam / N)) into a zeroed g from
                     # one trace; the residual launch below then only sums the loss
-                    g = t.zeros_like(d)
-                    if robust is not None:
+                    g = None if two_trace else t.zeros_like(d)
+                    if two_trace:
+                        f._forward_into(d, yhat_buf)
+                    elif poisson is not None:
+                        # (A^T(s + ((-s) y) / (f(d) + eps)) from the one trace)
+                        f._poisson_into(d, m64, s_res, poisson, yhat_buf, g)
+                    elif robust is not None:
                         # (a robust term: A^T(s psi(f(d) - y)), the fixed-point bound formed on
                         # the device from s)
                         # (s does not change: the record is written by the first iteration)
@@ -391,7 +414,15 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 # r * r (the loss) in one launch (csrc/loss.hip)
                 # (in the trace's ray order when the adjoint takes that: no permutation launch)
                 r_scaled = t.empty_like(yhat)
-                if robust is not None:
+                if poisson is not None:
+                    # (r_scaled = s_i + ((-s_i) y) / (f(d) + eps), and the partial sums of
+                    # w_i * (f(d) - y * log(f(d) + eps)))
+                    _lib.check(lib.sphrt_poisson_residual_f64(
+                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
+                        poisson, _lib.ptr(s_res), _lib.ptr(w_res), _lib.ptr(res_order),
+                        _lib.ptr(r_scaled), _lib.ptr(part_sq[it]), stream),
+                        'sphrt_poisson_residual_f64')
+                elif robust is not None:
                     # (r_scaled = psi(r) * s_i, and the partial sums of w_i * |r| or w_i * huber(r))
                     _lib.check(lib.sphrt_robust_residual_f64(
                         _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
@@ -412,6 +443,9 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 if not fused:
                     g = f._apply_adjoint(r_scaled, tuple(d.shape), d.dtype, d.device,
                                          trace_order=order is not None)
+                elif two_trace:
+                    g = t.empty_like(d)
+                    f._backproject_fixed_into(r_scaled, g, fixed[0])
                 if reduce is not None:
                     reduce(g)          # data-parallel: the sum of every rank's adjoint
                 if smooth is not None:
