@@ -628,6 +628,33 @@ int sphrt_cg_direction_f64(double *p, const double *r, int64_t n,
                            const double *part_rr_new, const double *part_rr, int64_t n_part,
                            const double *rr_stop, void *stream);
 
+/* ---- projected gradient with momentum: the vector side of an iteration (retrieval.fista) ------
+ * For min 1/2 x^T N x - b^T x subject to lower <= x <= upper, an iteration is g = N z - b without
+ * the damping term (the operator's entries and sphrt_smooth_reg_f64), then these two launches
+ * over the n elements of z, g, x_old, x_new (float64, distinct buffers), with the launch shape,
+ * the partition, sphrt_loss_partials and SUM(part) of the entries above.  The step and the
+ * restart decision never reach the host: `step` points to one float64 on the device (1 / L), and
+ * the first launch leaves the partial sums the second one's workgroups sum themselves.  Every
+ * product feeding a sum is a plain multiply and every update one fma; inf, NaN and denormals are
+ * not special-cased (a NaN u fails both compares and stays NaN; a NaN GD does not restart).
+ * lower / upper: -inf / +inf for no bound.  Each entry fails on the host, before any launch and
+ * without reading a pointer, on n <= 0, a null buffer, buffers that overlap, n_part != the
+ * partial count of a launch over n elements, n_omega < 2 and (the step entry) a NaN bound or
+ * lower >= upper.
+ *
+ *   gp = fma(c_damp, z[i], g[i]);  u = fma(-*step, gp, z[i])
+ *   x_new[i] = u < lower ? lower : (u > upper ? upper : u)
+ *   part_gd: partial sums of gp * (x_new[i] - x_old[i]);  part_mm: of (z[i] - x_new[i])^2      */
+int sphrt_pg_step_f64(const double *z, const double *g, const double *x_old, double *x_new,
+                      int64_t n, double c_damp, const double *step, double lower, double upper,
+                      double *part_gd, double *part_mm, void *stream);
+/*   GD = SUM(part_gd);  j = GD > 0 ? 1 : min(*j_in + 1, n_omega - 1), and at least 0
+ *   z[i] = fma(omega[j], x_new[i] - x_old[i], x_new[i]);  *j_out = j (thread 0 of workgroup 0,
+ *   an ordinary store; j_in != j_out: consecutive slots of the caller's restart record)         */
+int sphrt_pg_momentum_f64(double *z, const double *x_new, const double *x_old, int64_t n,
+                          const double *part_gd, int64_t n_part, const double *omega,
+                          int64_t n_omega, const int64_t *j_in, int64_t *j_out, void *stream);
+
 /* ---- fused no-store mode: trace + integrate in one pass (nothing persisted) --------------- */
 int sphrt_trace_integrate_f32(const sphrt_plan *plan, const sphrt_rays *rays,
                               const float *density, int64_t n_chan, int64_t chan_stride,

@@ -145,6 +145,10 @@ _SIGNATURES = [
     ('sphrt_cg_update_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
                                     c_vp]),
     ('sphrt_cg_direction_f64', c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    ('sphrt_pg_step_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_vp, c_dbl, c_dbl, c_vp,
+                                  c_vp, c_vp]),
+    ('sphrt_pg_momentum_f64', c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                      c_vp, c_vp]),
     ('sphrt_trace_integrate_f32', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_i64, c_i64,
                                           c_i64, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
     ('sphrt_trace_integrate_f64', c_int, [c_vp, ctypes.POINTER(RayBatch), c_vp, c_i64, c_i64,

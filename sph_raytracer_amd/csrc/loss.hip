@@ -16,6 +16,7 @@
 //
 // The vector side of retrieval.cg's iteration (two dot products, alpha, beta, three updates) is
 // here too, as three launches of the same shape that pass their scalars through partial sums.
+// So is the vector side of retrieval.fista's (step, clamp, restart, momentum), as two launches.
 #include "common.hpp"
 #include "stage.hpp"
 
@@ -434,9 +435,108 @@ __global__ __launch_bounds__(kLossThreads) void cg_direction_kernel(
     }
 }
 
+// ---- projected gradient with momentum (retrieval.fista): the vector side in two launches --------
+// The step 1 / L is read through a pointer (it is estimated on the device) and the restart
+// decision GD = SUM(part_gd) is formed by every workgroup of the second launch, in block_totals'
+// order, so neither reaches the host during a solve.
+
+// block_partial for two sums at once.
+__device__ __forceinline__ void block_partial2(double a, double b, double* out_a, double* out_b) {
+    __shared__ double sh[2][kLossThreads / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_xor(a, off);
+        b += __shfl_xor(b, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][threadIdx.x >> 6] = a;
+        sh[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sa = 0.0, sb = 0.0;
+        for (int i = 0; i < kLossThreads / 64; ++i) {
+            sa += sh[0][i];
+            sb += sh[1][i];
+        }
+        out_a[blockIdx.x] = sa;
+        out_b[blockIdx.x] = sb;
+    }
+}
+
+// block_totals for one sum (the same order).
+__device__ __forceinline__ double block_total(const double* __restrict__ pa, int n_part) {
+    __shared__ double sh[kLossThreads / 64];
+    double a = 0.0;
+    for (int j = threadIdx.x; j < n_part; j += kLossThreads) a += pa[j];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+    __syncthreads();
+    double ta = 0.0;
+    for (int i = 0; i < kLossThreads / 64; ++i) ta += sh[i];
+    return ta;
+}
+
+// g' = c_damp z + g, u = z - step g' (one fma each), x_new = u clamped by two compares (a NaN u
+// fails both and stays NaN; a bound that is hit is stored with the bound's own bits), and the
+// partial sums of g' (x_new - x_old) and of (z - x_new)^2.
+__global__ __launch_bounds__(kLossThreads) void pg_step_kernel(
+    const double* __restrict__ z, const double* __restrict__ g, const double* __restrict__ x_old,
+    double* __restrict__ x_new, int64_t n, double c_damp, const double* __restrict__ step,
+    double lower, double upper, double* __restrict__ part_gd, double* __restrict__ part_mm) {
+    const double neg_step = -*step;
+    double gd = 0.0, mm = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * kLossThreads) {
+        const double zi = z[i];
+        const double gp = fma(c_damp, zi, g[i]);
+        const double u = fma(neg_step, gp, zi);
+        const double xn = u < lower ? lower : (u > upper ? upper : u);
+        x_new[i] = xn;
+        const double dx = xn - x_old[i];
+        gd += gp * dx;
+        const double dz = zi - xn;
+        mm += dz * dz;
+    }
+    block_partial2(gd, mm, part_gd, part_mm);
+}
+
+// GD = SUM(part_gd); j = GD > 0 ? 1 : min(*j_in + 1, n_omega - 1) (a NaN GD fails the compare:
+// no restart); z = x_new + omega[j] (x_new - x_old) (one fma).  The thread's first elements are
+// loaded before the partials are summed.  j is kept inside the table whatever *j_in holds.
+__global__ __launch_bounds__(kLossThreads) void pg_momentum_kernel(
+    double* __restrict__ z, const double* __restrict__ x_new, const double* __restrict__ x_old,
+    int64_t n, const double* __restrict__ part_gd, int n_part, const double* __restrict__ omega,
+    int64_t n_omega, const int64_t* __restrict__ j_in, int64_t* __restrict__ j_out) {
+    const int64_t i0 = (int64_t)blockIdx.x * kLossThreads + threadIdx.x;
+    double a0 = 0.0, b0 = 0.0;
+    if (i0 < n) {
+        a0 = x_new[i0];
+        b0 = x_old[i0];
+    }
+    const int64_t jp = *j_in;
+    const double GD = block_total(part_gd, n_part);
+    int64_t j = GD > 0.0 ? 1 : (jp >= n_omega - 1 ? n_omega - 1 : jp + 1);
+    if (j < 0) j = 0;
+    const double w = omega[j];
+    for (int64_t i = i0; i < n; i += (int64_t)gridDim.x * kLossThreads) {
+        const bool first = i == i0;
+        const double xn = first ? a0 : x_new[i], xo = first ? b0 : x_old[i];
+        z[i] = fma(w, xn - xo, xn);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *j_out = j;
+}
+
 static unsigned loss_grid(int64_t n) {
     const int64_t b = (n + kLossThreads - 1) / kLossThreads;
     return (unsigned)(b < kLossMaxBlocks ? (b > 0 ? b : 1) : kLossMaxBlocks);
+}
+
+// Do two buffers of na and nb bytes share a byte (addresses compared as integers; nothing read).
+static bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb ? pb - pa < (uintptr_t)na : pa - pb < (uintptr_t)nb;
 }
 
 // The host refusals the three cg entries share: the length and the count of partial sums that a
@@ -672,4 +772,58 @@ extern "C" int sphrt_cg_direction_f64(double* p, const double* r, int64_t n,
     hipLaunchKernelGGL(cg_direction_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
                        (hipStream_t)stream, p, r, n, part_rr_new, part_rr, (int)n_part, rr_stop);
     return check_launch("cg_direction");
+}
+
+extern "C" int sphrt_pg_step_f64(const double* z, const double* g, const double* x_old,
+                                 double* x_new, int64_t n, double c_damp, const double* step,
+                                 double lower, double upper, double* part_gd, double* part_mm,
+                                 void* stream) {
+    const char* me = "sphrt_pg_step_f64";
+    if (int e = refuse_cg(me, n, 0, false)) return e;
+    if (!z || !g || !x_old || !x_new || !step || !part_gd || !part_mm)
+        return fail("%s: null buffer", me);
+    if (lower != lower || upper != upper || !(lower < upper))
+        return fail("%s: bounds need lower < upper, neither NaN (%g, %g)", me, lower, upper);
+    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
+    const void* vec[4] = {z, g, x_old, x_new};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            if (overlap(vec[a], nb, vec[b], nb)) return fail("%s: aliased vectors", me);
+        if (overlap(vec[a], nb, part_gd, pb) || overlap(vec[a], nb, part_mm, pb) ||
+            overlap(vec[a], nb, step, sizeof(double)))
+            return fail("%s: a vector aliased with the partial sums or the step", me);
+    }
+    if (overlap(part_gd, pb, part_mm, pb) || overlap(part_gd, pb, step, sizeof(double)) ||
+        overlap(part_mm, pb, step, sizeof(double)))
+        return fail("%s: aliased partial sums", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(pg_step_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, z, g, x_old, x_new, n, c_damp, step, lower, upper,
+                       part_gd, part_mm);
+    return check_launch("pg_step");
+}
+
+extern "C" int sphrt_pg_momentum_f64(double* z, const double* x_new, const double* x_old,
+                                     int64_t n, const double* part_gd, int64_t n_part,
+                                     const double* omega, int64_t n_omega, const int64_t* j_in,
+                                     int64_t* j_out, void* stream) {
+    const char* me = "sphrt_pg_momentum_f64";
+    if (int e = refuse_cg(me, n, n_part, true)) return e;
+    if (!z || !x_new || !x_old || !part_gd || !omega || !j_in || !j_out)
+        return fail("%s: null buffer", me);
+    if (n_omega < 2) return fail("%s: n_omega %lld, the table holds at least two factors", me,
+                                 (long long)n_omega);
+    const int64_t nb = n * (int64_t)sizeof(double), pb = n_part * (int64_t)sizeof(double);
+    if (overlap(z, nb, x_new, nb) || overlap(z, nb, x_old, nb) || overlap(x_new, nb, x_old, nb))
+        return fail("%s: aliased vectors", me);
+    if (overlap(j_in, sizeof(int64_t), j_out, sizeof(int64_t)))
+        return fail("%s: aliased j_in and j_out", me);
+    if (overlap(z, nb, part_gd, pb) || overlap(z, nb, omega, n_omega * (int64_t)sizeof(double)) ||
+        overlap(z, nb, j_in, sizeof(int64_t)) || overlap(z, nb, j_out, sizeof(int64_t)))
+        return fail("%s: z aliased with an input", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(pg_momentum_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, z, x_new, x_old, n, part_gd, (int)n_part, omega,
+                       n_omega, j_in, j_out);
+    return check_launch("pg_momentum");
 }

@@ -608,46 +608,46 @@ def cg(f, y, loss_fns=[SquareLoss()], x0=None, num_iterations=50, damp=0.0, tol=
     return _cg_generic(f, y, sq, smooth, x0, num_iterations, float(damp), float(tol), bar)
 
 
-def _cg_terms(y, loss_fns, damp, tol, num_iterations):
+def _cg_terms(y, loss_fns, damp, tol, num_iterations, who='cg'):
     """(the SquareLoss, the SmoothRegularizer or None) of a total `cg` solves; ValueError naming
-    what it does not."""
+    what it does not.  `fista` takes the same totals by the same rules, under its own name."""
     if not isinstance(y, t.Tensor):
-        raise ValueError(f'cg needs measurements y as a tensor, not {type(y).__name__}')
+        raise ValueError(f'{who} needs measurements y as a tensor, not {type(y).__name__}')
     for name, v in (('damp', damp), ('tol', tol)):
         if not _number(v) or not 0 <= v < float('inf'):
-            raise ValueError(f'cg needs a finite {name} >= 0, not {v!r}')
+            raise ValueError(f'{who} needs a finite {name} >= 0, not {v!r}')
     if isinstance(num_iterations, bool) or not isinstance(num_iterations, int) \
             or num_iterations < 0:
-        raise ValueError(f'cg needs num_iterations as an integer >= 0, not {num_iterations!r}')
+        raise ValueError(f'{who} needs num_iterations as an integer >= 0, not {num_iterations!r}')
     sq = smooth = None
     for fn in loss_fns:
         name = type(fn).__name__
         if type(fn) is SquareLoss:
             if sq is not None:
-                raise ValueError('cg solves for one SquareLoss, not two')
+                raise ValueError(f'{who} solves for one SquareLoss, not two')
             sq = fn
         elif type(fn) is SmoothRegularizer:
             if smooth is not None:
-                raise ValueError('cg solves with at most one SmoothRegularizer, not two')
+                raise ValueError(f'{who} solves with at most one SmoothRegularizer, not two')
             if fn.smooth_kind != 'square':
-                raise ValueError(f"cg needs a quadratic total: SmoothRegularizer(kind="
+                raise ValueError(f"{who} needs a quadratic total: SmoothRegularizer(kind="
                                  f"{fn.smooth_kind!r}) is not (kind='square' is)")
             smooth = fn
         else:
-            raise ValueError(f'cg needs a quadratic total of one SquareLoss and at most one '
+            raise ValueError(f'{who} needs a quadratic total of one SquareLoss and at most one '
                              f"SmoothRegularizer(kind='square'): {name} is neither (gd takes it)")
         if not fn.use_grad:
-            raise ValueError(f'cg: {name}(use_grad=False) is a monitor, not a term of the total')
+            raise ValueError(f'{who}: {name}(use_grad=False) is a monitor, not a term of the total')
         if not _number(fn.lam) or not math.isfinite(fn.lam):
-            raise ValueError(f'cg needs a finite scalar lam, not {name}.lam = {fn.lam!r}')
+            raise ValueError(f'{who} needs a finite scalar lam, not {name}.lam = {fn.lam!r}')
         if not _unit(fn.volume_mask):
-            raise ValueError(f'cg does not take a volume_mask ({name})')
+            raise ValueError(f'{who} does not take a volume_mask ({name})')
         if not _unit(fn.projection_mask) and not (fn is sq and _ray_mask(fn.projection_mask, y)):
-            raise ValueError(f'cg: the projection_mask of {name} must be 1' + (
+            raise ValueError(f'{who}: the projection_mask of {name} must be 1' + (
                 ' or a bool / float32 / float64 tensor on the device of y that broadcasts to '
                 'its shape' if fn is sq else ''))
     if sq is None:
-        raise ValueError('cg needs one SquareLoss among loss_fns')
+        raise ValueError(f'{who} needs one SquareLoss among loss_fns')
     return sq, smooth
 
 
@@ -679,6 +679,31 @@ def _cg_info(rr, stop):
     return {'residual': hist, 'converged_at': at}
 
 
+def _normal_generic(f, yd, sq, smooth, x):
+    """normal(d, m) = A^T(s (A d - m)) + G d in plain torch, through f(d) and f._apply_adjoint
+    alone (m = None: no measurements), for volumes like `x`: what `_cg_generic` and
+    `_fista_generic` iterate (the damping term is theirs)."""
+    dshape, dtype, dev = tuple(x.shape), x.dtype, x.device
+    c_sq = sq.lam / yd.numel()
+    s = 2 * c_sq if _unit(sq.projection_mask) else \
+        (c_sq * sq.projection_mask.detach().to(t.promote_types(yd.dtype, dtype))) * 2
+
+    def smooth_grad(d):
+        # (linear in d: the square kind's gradient, lam and 1 / V included)
+        with t.enable_grad():
+            leaf = d.detach().requires_grad_()
+            g, = t.autograd.grad(smooth(f, yd, leaf, leaf), leaf)
+        return g
+
+    def normal(d, m):
+        q = f(d)
+        h = f._apply_adjoint(s * (q if m is None else q - m), dshape, dtype, dev)
+        if smooth is not None:
+            h = h + smooth_grad(d)
+        return h
+    return normal
+
+
 def _cg_generic(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
     """`cg` in plain torch, through f(x) and f._apply_adjoint alone: the specification of
     `_cg_direct` (the same guards in the same places; sums in torch's order) and what runs on
@@ -687,25 +712,12 @@ def _cg_generic(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
         yd = y.detach()
         x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=yd.device) if x0 is None \
             else t.as_tensor(x0).detach().clone()
-        dshape, dtype, dev = tuple(x.shape), x.dtype, x.device
-        c_sq, c = sq.lam / yd.numel(), 2 * damp / x.numel()
-        s = 2 * c_sq if _unit(sq.projection_mask) else \
-            (c_sq * sq.projection_mask.detach().to(t.promote_types(yd.dtype, dtype))) * 2
-
-        def smooth_grad(d):
-            # (linear in d: the square kind's gradient, lam and 1 / V included)
-            with t.enable_grad():
-                leaf = d.detach().requires_grad_()
-                g, = t.autograd.grad(smooth(f, yd, leaf, leaf), leaf)
-            return g
+        c = 2 * damp / x.numel()
+        normal = _normal_generic(f, yd, sq, smooth, x)
 
         def gradient(d, m):
             """A^T(s (A d - m)) + G d + c d: grad J(d) with m = y, N d with m = None."""
-            q = f(d)
-            h = f._apply_adjoint(s * (q if m is None else q - m), dshape, dtype, dev)
-            if smooth is not None:
-                h = h + smooth_grad(d)
-            return t.add(h, d, alpha=c)
+            return t.add(normal(d, m), d, alpha=c)
 
         def frozen(v):
             return v <= stop if stop is not None else t.zeros_like(v, dtype=t.bool)
@@ -751,12 +763,104 @@ def _kernel_sum(part):
     return ((((0.0 + v[:, 0]) + v[:, 1]) + v[:, 2]) + v[:, 3]).reshape(part.shape[:-1])
 
 
+def _normal_direct(f, y, sq, smooth, x):
+    """apply(d) / apply(d, against_y=True) = A^T(s (A d - m)) + G d, m = 0 or y, on the operator's
+    own entries (`_cg_is_direct`), for contiguous float64 volumes like `x` on the operator's GPU:
+    what `_cg_direct` and `_fista_direct` iterate (the damping term is theirs).  Over a
+    MatrixFreeOperator one trace (`_normal_into`: q = A d and A^T(s (q - m))); over an Operator
+    the loop's forward, the residual kernel (s (q - m) in the adjoint's order) and the adjoint;
+    then, with a smooth term, one sphrt_smooth_reg_f64 launch.  The result is a buffer the next
+    application may overwrite.  -> (apply, the count of partial sums of a launch over a volume)."""
+    from . import _lib
+    from .raytracer import MatrixFreeOperator, _scale_max
+    lib = _lib.load()
+    fused = isinstance(f, MatrixFreeOperator)
+    dev, f64 = f._cdev, t.float64
+    yd = y.detach().contiguous()
+    y_f64 = int(yd.dtype == f64)
+    n_meas, n_vox = yd.numel(), x.numel()
+    c_sq = sq.lam / n_meas
+    w_res = s_res = None
+    if isinstance(sq.projection_mask, t.Tensor):     # as _gd_direct forms them
+        w_res = sq.projection_mask.detach().to(f64).expand(yd.shape).contiguous().reshape(-1)
+        s_res = (c_sq * w_res) * 2
+    pn, ps = lib.sphrt_loss_partials(n_vox), lib.sphrt_loss_partials(n_meas)
+    part_tmp = t.empty(max(pn, ps), dtype=f64, device=dev)   # (sums nobody reads)
+    wrap = smooth.wraps(f) if smooth is not None else None
+    q_buf = t.empty(n_meas, dtype=f64, device=dev)
+    zero_m = t.zeros(n_meas, dtype=f64, device=dev)
+    if fused:
+        m64 = yd.to(f64).reshape(-1)
+        weighted = None if s_res is None else \
+            (s_res, _scale_max(s_res) if f.deterministic else None)
+        fixed = (f._fixed_buffers(),) if f.deterministic else ()
+        h_buf = t.empty_like(x)
+
+        def normal(d, against_y):
+            """A^T(s (A d - m)), m = y or 0, into h_buf from one trace."""
+            if not fixed:
+                h_buf.zero_()
+            f._normal_into(d, m64 if against_y else zero_m, 2 * c_sq, q_buf, h_buf, *fixed,
+                           weighted=weighted)
+            return h_buf
+    else:
+        # the loop's forward descriptor, the adjoint's input order and the measurements in
+        # that order, as _gd_direct sets them up (the brick-staged forward packs d itself)
+        staged = f._stage_for_loop(f64)
+        if staged is not None and f._csr['n'] != n_meas:
+            staged = None
+        order = f._adjoint_trace_order()
+        if order is not None and order.numel() != n_meas:
+            order = None
+        loop_desc = staged[0] if staged is not None else None
+        y_res, res_order, keep_rows = yd.reshape(-1), order, None
+        if order is not None:
+            sd = loop_desc if loop_desc is not None else f._loop_descriptor(f64)
+            keep_rows = f._trace_position_rows(sd) if sd is not None else None
+            if keep_rows is not None:
+                loop_desc = sd
+                y_res, res_order = y_res.index_select(0, f._ray_id_long()), None
+                if w_res is not None:
+                    w_res, s_res = (v.index_select(0, f._ray_id_long())
+                                    for v in (w_res, s_res))
+        rs_buf = t.empty(n_meas, dtype=f64, device=dev)
+
+        def normal(d, against_y):
+            """A^T(s (A d - m)), m = y or 0: forward, scaled residual, adjoint."""
+            stream = _lib.stream_of(dev)
+            if loop_desc is not None:
+                f._forward_staged(d, q_buf, loop_desc)
+                q = q_buf
+            else:
+                q = f(d).reshape(-1)
+            m, m_f64 = (y_res, y_f64) if against_y else (zero_m, 1)
+            if w_res is None:
+                _lib.check(lib.sphrt_sq_residual_f64(
+                    _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, 2 * c_sq, _lib.ptr(res_order),
+                    _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream), 'sphrt_sq_residual_f64')
+            else:
+                _lib.check(lib.sphrt_wsq_residual_f64(
+                    _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, _lib.ptr(s_res), _lib.ptr(w_res),
+                    _lib.ptr(res_order), _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream),
+                    'sphrt_wsq_residual_f64')
+            return f._apply_adjoint(rs_buf.view(yd.shape), tuple(d.shape), d.dtype, dev,
+                                    trace_order=order is not None)
+
+    def apply(d, against_y=False):
+        h = normal(d, against_y)
+        if smooth is not None:
+            smooth._launch(d, wrap, smooth.lam, 0.0, h, h, part_tmp, None)
+        return h
+    return apply, pn
+
+
 def _cg_direct(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
     """`cg` on the operator's own entries (`_cg_is_direct`).  An iteration is h = N p — over a
     MatrixFreeOperator one trace (`_normal_into` against zero measurements: q = A p and
     A^T(s q)), over an Operator the loop's forward, the residual kernel against zero
     measurements (s q in the adjoint's order) and the adjoint; then, with a smooth term, one
-    sphrt_smooth_reg_f64 launch (h += G p) — followed by three csrc/loss.hip launches:
+    sphrt_smooth_reg_f64 launch (h += G p): `_normal_direct`, which `_fista_direct` shares —
+    followed by three csrc/loss.hip launches:
     sphrt_cg_curvature_f64 (h += c p, partial sums of p h), sphrt_cg_update_f64 (alpha from the
     partial sums; x += alpha p, r -= alpha h, partial sums of r r) and sphrt_cg_direction_f64
     (beta; p = r + beta p).  alpha, beta and the freeze live on the device, formed by every
@@ -766,91 +870,21 @@ def _cg_direct(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
     operator's entries against y, the smooth launch and the curvature launch on x0, and an update
     launch with alpha = 1 on zeroed r and p (r = -g, x unchanged, the partial sums of r r)."""
     from . import _lib
-    from .raytracer import MatrixFreeOperator, _scale_max
     lib = _lib.load()
-    fused = isinstance(f, MatrixFreeOperator)
     dev, f64 = f._cdev, t.float64
-    yd = y.detach().contiguous()
-    y_f64 = int(yd.dtype == f64)
     with t.no_grad(), t.cuda.device(dev):
         x = t.zeros(tuple(f.grid.shape), dtype=f64, device=dev) if x0 is None \
             else x0.detach().clone()
-        n_meas, n_vox = yd.numel(), x.numel()
-        c_sq, c = sq.lam / n_meas, 2 * damp / n_vox
-        w_res = s_res = None
-        if isinstance(sq.projection_mask, t.Tensor):     # as _gd_direct forms them
-            w_res = sq.projection_mask.detach().to(f64).expand(yd.shape).contiguous().reshape(-1)
-            s_res = (c_sq * w_res) * 2
+        n_vox = x.numel()
+        c = 2 * damp / n_vox
         r, p = t.zeros_like(x), t.zeros_like(x)
-        pn, ps = lib.sphrt_loss_partials(n_vox), lib.sphrt_loss_partials(n_meas)
+        apply, pn = _normal_direct(f, y, sq, smooth, x)
         part_rr = t.empty((num_iterations + 1, pn), dtype=f64, device=dev)
         part_php = t.empty(pn, dtype=f64, device=dev)
-        part_tmp = t.empty(max(pn, ps), dtype=f64, device=dev)   # (sums nobody reads)
-        wrap = smooth.wraps(f) if smooth is not None else None
-        q_buf = t.empty(n_meas, dtype=f64, device=dev)
-        zero_m = t.zeros(n_meas, dtype=f64, device=dev)
-        if fused:
-            m64 = yd.to(f64).reshape(-1)
-            weighted = None if s_res is None else \
-                (s_res, _scale_max(s_res) if f.deterministic else None)
-            fixed = (f._fixed_buffers(),) if f.deterministic else ()
-            h_buf = t.empty_like(x)
-
-            def normal(d, against_y):
-                """A^T(s (A d - m)), m = y or 0, into h_buf from one trace."""
-                if not fixed:
-                    h_buf.zero_()
-                f._normal_into(d, m64 if against_y else zero_m, 2 * c_sq, q_buf, h_buf, *fixed,
-                               weighted=weighted)
-                return h_buf
-        else:
-            # the loop's forward descriptor, the adjoint's input order and the measurements in
-            # that order, as _gd_direct sets them up (the brick-staged forward packs d itself)
-            staged = f._stage_for_loop(f64)
-            if staged is not None and f._csr['n'] != n_meas:
-                staged = None
-            order = f._adjoint_trace_order()
-            if order is not None and order.numel() != n_meas:
-                order = None
-            loop_desc = staged[0] if staged is not None else None
-            y_res, res_order, keep_rows = yd.reshape(-1), order, None
-            if order is not None:
-                sd = loop_desc if loop_desc is not None else f._loop_descriptor(f64)
-                keep_rows = f._trace_position_rows(sd) if sd is not None else None
-                if keep_rows is not None:
-                    loop_desc = sd
-                    y_res, res_order = y_res.index_select(0, f._ray_id_long()), None
-                    if w_res is not None:
-                        w_res, s_res = (v.index_select(0, f._ray_id_long())
-                                        for v in (w_res, s_res))
-            rs_buf = t.empty(n_meas, dtype=f64, device=dev)
-
-            def normal(d, against_y):
-                """A^T(s (A d - m)), m = y or 0: forward, scaled residual, adjoint."""
-                stream = _lib.stream_of(dev)
-                if loop_desc is not None:
-                    f._forward_staged(d, q_buf, loop_desc)
-                    q = q_buf
-                else:
-                    q = f(d).reshape(-1)
-                m, m_f64 = (y_res, y_f64) if against_y else (zero_m, 1)
-                if w_res is None:
-                    _lib.check(lib.sphrt_sq_residual_f64(
-                        _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, 2 * c_sq, _lib.ptr(res_order),
-                        _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream), 'sphrt_sq_residual_f64')
-                else:
-                    _lib.check(lib.sphrt_wsq_residual_f64(
-                        _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, _lib.ptr(s_res), _lib.ptr(w_res),
-                        _lib.ptr(res_order), _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream),
-                        'sphrt_wsq_residual_f64')
-                return f._apply_adjoint(rs_buf.view(yd.shape), tuple(d.shape), d.dtype, dev,
-                                        trace_order=order is not None)
 
         def curvature(d, against_y):
             """h = A^T(s (A d - m)) + G d + c d and the partial sums of d h (part_php)."""
-            h = normal(d, against_y)
-            if smooth is not None:
-                smooth._launch(d, wrap, smooth.lam, 0.0, h, h, part_tmp, None)
+            h = apply(d, against_y)
             _lib.check(lib.sphrt_cg_curvature_f64(_lib.ptr(d), _lib.ptr(h), n_vox, c,
                                                   _lib.ptr(part_php), _lib.stream_of(dev)),
                        'sphrt_cg_curvature_f64')
@@ -884,3 +918,199 @@ def _cg_direct(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
         sums = _kernel_sum(part_rr[:done + 1])
         host = (t.cat([sums, stop]) if stop is not None else sums).cpu().tolist()
     return x, y_hat, _cg_info(host[:done + 1], host[-1] if stop is not None else None)
+
+
+# ---- bound-constrained solver: projected gradient with momentum -----------------------------------
+
+# The step-size estimate ("Bound-constrained solver": the study that chose them).
+_FISTA_POWER_ITERATIONS = 10
+_FISTA_MARGIN = 0.3
+
+
+def fista(f, y, loss_fns=[SquareLoss()], x0=None, num_iterations=100, damp=0.0, lower=0.0,
+          upper=None, lipschitz=None, power_iterations=_FISTA_POWER_ITERATIONS,
+          progress_bar=False):
+    """Minimise the total `cg` solves,
+
+        J(x) = lam_f * mean(w * (y - f(x))^2) + lam_s * SmoothRegularizer(kind='square')(x)
+               + damp * mean(x^2),
+
+    subject to lower <= x <= upper elementwise, by FISTA with a fixed step 1 / L and a gradient
+    restart -> (x, f(x), info).  Every iterate, the returned one included, satisfies the bounds
+    exactly.  `lower` / `upper`: Python numbers with lower < upper, None for no bound on that
+    side.  `loss_fns`, `damp` and `num_iterations` by `cg`'s rules (anything not quadratic raises
+    ValueError naming the term).
+
+    With grad J(x) = N x - b (`cg`'s docstring), x_0 = z_0 = clamp(x0 or zeros), j = 0 and the
+    momentum table OMEGA (`_fista_omega`), iteration k is
+
+        g  = N z - b                       (the damping term by one fma: g = fma(c, z, .))
+        u  = fma(-1 / L, g, z);  x_{k+1} = u < lower ? lower : (u > upper ? upper : u)
+        GD = sum g (x_{k+1} - x_k);  MM = sum (z - x_{k+1})^2
+        j  = 1 if GD > 0 else j + 1        (the restart; a NaN GD does not restart)
+        z  = fma(OMEGA[j], x_{k+1} - x_k, x_{k+1})
+
+    L must be at least the largest eigenvalue of N.  `lipschitz`: a finite number > 0, or None:
+    the Rayleigh quotient after `power_iterations` steps of the power method on N from the
+    all-ones volume, times 1 + 0.3 (it is a lower bound; the margin and the default count are
+    measured in DESIGN §5).  info = {'residual': [sqrt(MM_k / MM_0) for k = 0 .. K - 1] (0.0
+    where MM_k is exactly zero), 'restarts': the iterations k >= 1 at which j was reset,
+    'lipschitz': L}.  There is no tolerance and no early exit.
+
+    The inputs `cg` runs directly (`_cg_is_direct`) run `_fista_direct`: the operator's own
+    launches and two csrc/loss.hip launches per iteration, L, the step and the restart decision
+    on the device, the whole solve enqueued without a host sync and bitwise reproducible where
+    the adjoint is.  Everything else runs the same algorithm in plain torch (`_fista_generic`)."""
+    sq, smooth = _cg_terms(y, loss_fns, damp, 0.0, num_iterations, who='fista')
+    bounds = []
+    for name, v, none in (('lower', lower, -math.inf), ('upper', upper, math.inf)):
+        if v is None:
+            v = none
+        if not _number(v) or math.isnan(v):
+            raise ValueError(f'fista needs {name} as a number (not NaN) or None, not {v!r}')
+        bounds.append(float(v))
+    if not bounds[0] < bounds[1]:
+        raise ValueError(f'fista needs lower < upper, not lower = {lower!r}, upper = {upper!r}')
+    if lipschitz is not None and (not _number(lipschitz) or not 0 < lipschitz < math.inf):
+        raise ValueError(f'fista needs a finite lipschitz > 0 (or None), not {lipschitz!r}')
+    if isinstance(power_iterations, bool) or not isinstance(power_iterations, int) \
+            or power_iterations < 1:
+        raise ValueError(f'fista needs power_iterations as an integer >= 1, not '
+                         f'{power_iterations!r}')
+    bar = _Bar(range(num_iterations), progress_bar)
+    run = _fista_direct if _cg_is_direct(f, y, x0) else _fista_generic
+    return run(f, y, sq, smooth, x0, num_iterations, float(damp), bounds[0], bounds[1],
+               None if lipschitz is None else float(lipschitz), power_iterations, bar)
+
+
+def _fista_omega(num_iterations):
+    """The momentum table as Python floats, length num_iterations + 1: OMEGA[0] = OMEGA[1] = 0
+    and OMEGA[j] = (t_j - 1) / t_{j+1} with t_1 = 1, t_{j+1} = (1 + sqrt(1 + 4 t_j^2)) / 2."""
+    omega, tj = [0.0], 1.0
+    for _ in range(num_iterations):
+        tn = (1.0 + math.sqrt(1.0 + 4.0 * tj * tj)) / 2.0
+        omega.append((tj - 1.0) / tn)
+        tj = tn
+    return omega
+
+
+def _fista_step(matvec, like, lipschitz, power_iterations):
+    """(L, 1 / L) as one-element tensors on the device of `like`, nothing read back.  lipschitz
+    None: v = ones; `power_iterations` times: w = N v (`matvec`), rho = v.w / v.v, v = w / |w|;
+    L = rho (1 + margin).  An L that is not > 0 (N = 0: every x is a minimiser) gives a step of 0
+    instead of a division by it."""
+    if lipschitz is not None:
+        L = t.full((1,), lipschitz, dtype=like.dtype, device=like.device)
+    else:
+        v = t.ones_like(like)
+        for _ in range(power_iterations):
+            w = matvec(v)
+            rho = (v * w).sum() / (v * v).sum()
+            v = w / w.norm()
+        L = (rho * (1.0 + _FISTA_MARGIN)).reshape(1)
+    return L, t.where(L > 0, 1.0 / L, t.zeros_like(L))
+
+
+def _fista_info(mm, jrec, L):
+    """`fista`'s info from MM_k (k = 0 .. K - 1), the record of j (K + 1 entries) and L, on the
+    host."""
+    mm0 = mm[0] if mm else 0.0
+    hist = [0.0 if v == 0 else math.sqrt(v / mm0) if mm0 > 0 else float('nan') for v in mm]
+    return {'residual': hist, 'lipschitz': L,
+            'restarts': [k for k in range(1, len(jrec) - 1) if jrec[k + 1] == 1]}
+
+
+def _fista_generic(f, y, sq, smooth, x0, num_iterations, damp, lower, upper, lipschitz,
+                   power_iterations, bar):
+    """`fista` in plain torch, through f(x) and f._apply_adjoint alone: the specification of
+    `_fista_direct` (sums in torch's order) and what runs on the CPU.  Every scalar, j included,
+    stays a tensor on the device: no sync inside the loop."""
+    with t.no_grad():
+        yd = y.detach()
+        x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=yd.device) if x0 is None \
+            else t.as_tensor(x0).detach().clone()
+        c = 2 * damp / x.numel()
+        normal = _normal_generic(f, yd, sq, smooth, x)
+        lo, hi = (t.full((), v, dtype=x.dtype, device=x.device) for v in (lower, upper))
+
+        def clamp(u):
+            return t.where(u < lo, lo, t.where(u > hi, hi, u))
+
+        L, step = _fista_step(lambda v: t.add(normal(v, None), v, alpha=c), x, lipschitz,
+                              power_iterations)
+        x = clamp(x)
+        z = x
+        omega = t.tensor(_fista_omega(num_iterations), dtype=x.dtype, device=x.device)
+        j = t.zeros(1, dtype=t.int64, device=x.device)
+        one, mms, js = t.ones_like(j), [], [j]
+        try:
+            for _ in bar:
+                g = t.add(normal(z, yd), z, alpha=c)
+                x_new = clamp(t.addcmul(z, g, -step))
+                gd = (g * (x_new - x)).sum()
+                mm = ((z - x_new) ** 2).sum()
+                j = t.where(gd > 0, one, j + 1)
+                z = t.addcmul(x_new, x_new - x, omega.index_select(0, j))
+                x = x_new
+                mms.append(mm)
+                js.append(j)
+        except KeyboardInterrupt:
+            pass
+        y_hat = f(x)
+        done = len(mms)
+        host = t.cat([t.stack(mms).to(t.float64) if done else L.new_zeros(0).to(t.float64),
+                      t.cat(js).to(t.float64), L.to(t.float64)]).cpu().tolist()
+    return x, y_hat, _fista_info(host[:done], host[done:2 * done + 1], host[-1])
+
+
+def _fista_direct(f, y, sq, smooth, x0, num_iterations, damp, lower, upper, lipschitz,
+                  power_iterations, bar):
+    """`fista` on the operator's own entries (`_cg_is_direct`).  An iteration is g = N z - b
+    without the damping term (`_normal_direct` against y: over a MatrixFreeOperator one trace,
+    over an Operator its forward, residual and adjoint launches; the smooth launch with a smooth
+    term) followed by two csrc/loss.hip launches: sphrt_pg_step_f64 (the damping term, the step,
+    the clamp into the other of two x buffers, partial sums of GD and MM) and
+    sphrt_pg_momentum_f64 (GD from the partial sums in every workgroup, j, z, and j into the next
+    slot of a (K + 1,) int64 record).  The step 1 / L is a one-element device tensor the step
+    launch reads through a pointer — the power method runs in torch over the same application —
+    so nothing is read back before the loop ends; then MM_k is one row of partial sums per
+    iteration (`_kernel_sum`), and the record of j gives the restarts."""
+    from . import _lib
+    lib = _lib.load()
+    dev, f64 = f._cdev, t.float64
+    with t.no_grad(), t.cuda.device(dev):
+        x = t.zeros(tuple(f.grid.shape), dtype=f64, device=dev) if x0 is None \
+            else x0.detach().clone()
+        n_vox = x.numel()
+        c = 2 * damp / n_vox
+        apply, pn = _normal_direct(f, y, sq, smooth, x)
+        L, step = _fista_step(lambda v: t.add(apply(v), v, alpha=c), x, lipschitz,
+                              power_iterations)
+        lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
+        x = t.where(x < lo, lo, t.where(x > hi, hi, x))
+        x_new, z = t.empty_like(x), x.clone()
+        omega = t.tensor(_fista_omega(num_iterations), dtype=f64, device=dev)
+        jrec = t.zeros(num_iterations + 1, dtype=t.int64, device=dev)
+        part_gd = t.empty(pn, dtype=f64, device=dev)
+        part_mm = t.empty((max(num_iterations, 1), pn), dtype=f64, device=dev)
+        done = 0
+        try:
+            for it in bar:
+                g = apply(z, True)
+                stream = _lib.stream_of(dev)
+                _lib.check(lib.sphrt_pg_step_f64(
+                    _lib.ptr(z), _lib.ptr(g), _lib.ptr(x), _lib.ptr(x_new), n_vox, c,
+                    _lib.ptr(step), lower, upper, _lib.ptr(part_gd), _lib.ptr(part_mm[it]),
+                    stream), 'sphrt_pg_step_f64')
+                _lib.check(lib.sphrt_pg_momentum_f64(
+                    _lib.ptr(z), _lib.ptr(x_new), _lib.ptr(x), n_vox, _lib.ptr(part_gd), pn,
+                    _lib.ptr(omega), omega.numel(), _lib.ptr(jrec[it:]), _lib.ptr(jrec[it + 1:]),
+                    stream), 'sphrt_pg_momentum_f64')
+                x, x_new = x_new, x
+                done = it + 1
+        except KeyboardInterrupt:
+            pass
+        y_hat = f(x)       # (goes out before the readback waits)
+        mm = _kernel_sum(part_mm[:done]) if done else L.new_zeros(0)
+        host = t.cat([mm, jrec[:done + 1].to(f64), L]).cpu().tolist()
+    return x, y_hat, _fista_info(host[:done], host[done:2 * done + 1], host[-1])
