@@ -897,8 +897,10 @@ def _cg_direct(f, y, sq, smooth, x0, num_iterations, damp, tol, bar):
                 'sphrt_cg_update_f64')
 
         # r_0 = -grad J(x0) and its partial sums: an update with alpha = 1 / 1 on r = p = 0
+        # (a fill launch: `one[0] = 1.0` copies a host scalar into the 0-dim view, a pageable
+        # copy that synchronises the host with the stream)
         one = t.zeros(pn, dtype=f64, device=dev)
-        one[0] = 1.0
+        one[:1].fill_(1.0)
         update(curvature(x, True), one, one, None, part_rr[0])
         p.copy_(r)
         stop = (_kernel_sum(part_rr[0]) * (tol * tol)).reshape(1) if tol > 0 else None
@@ -1089,7 +1091,10 @@ def _fista_direct(f, y, sq, smooth, x0, num_iterations, damp, lower, upper, lips
         lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
         x = t.where(x < lo, lo, t.where(x > hi, hi, x))
         x_new, z = t.empty_like(x), x.clone()
-        omega = t.tensor(_fista_omega(num_iterations), dtype=f64, device=dev)
+        # (from pinned memory, not waited for: a tensor built on the device from a Python list is
+        # a pageable copy, which synchronises the host with the stream)
+        omega = t.tensor(_fista_omega(num_iterations), dtype=f64, pin_memory=True).to(
+            dev, non_blocking=True)
         jrec = t.zeros(num_iterations + 1, dtype=t.int64, device=dev)
         part_gd = t.empty(pn, dtype=f64, device=dev)
         part_mm = t.empty((max(num_iterations, 1), pn), dtype=f64, device=dev)
