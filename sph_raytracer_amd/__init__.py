@@ -5,7 +5,7 @@
 from .raytracer import MatrixFreeOperator, Operator, back_project, line_integrals
 from .geometry import *  # noqa: F401,F403
 from .geometry import __all__ as _geometry_all
-from .retrieval import cg, fista, gd
+from .retrieval import cg, fista, gd, primal_dual
 
 __all__ = ['Operator', 'MatrixFreeOperator', 'back_project', 'line_integrals', 'gd', 'cg',
-           'fista'] + list(_geometry_all)
+           'fista', 'primal_dual'] + list(_geometry_all)

@@ -193,6 +193,15 @@ _SIGNATURES = [
                                        c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
 ]
 EXPORTED = [s[0] for s in _SIGNATURES]
+# the same for include/sphrt_pd.h (retrieval.primal_dual's two launches), a table of its own as
+# the header is
+_PD_SIGNATURES = [
+    ('sphrt_pd_primal_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_dbl, c_vp, c_dbl, c_dbl, c_vp, c_vp]),
+    ('sphrt_pd_dual_f64', c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp]),
+]
+PD_EXPORTED = [s[0] for s in _PD_SIGNATURES]
 # sphrt_exact_sort_lists methods and info fields (sphrt.h)
 SORT_SERIAL_AOS, SORT_SERIAL_SOA, SORT_WAVE1, SORT_WAVE4, SORT_NETWORK = range(5)
 SORT_INFO_FIELDS = 4
@@ -218,7 +227,7 @@ def load():
     lib.sphrt_version.argtypes = []
     if not os.environ.get('SPHRT_LIB'):   # an A/B variant may come from other sources
         _check_hash(lib.sphrt_version().decode(), LIB_PATH)
-    for name, res, args in _SIGNATURES:
+    for name, res, args in _SIGNATURES + _PD_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:

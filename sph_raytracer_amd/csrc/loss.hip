@@ -16,9 +16,11 @@
 //
 // The vector side of retrieval.cg's iteration (two dot products, alpha, beta, three updates) is
 // here too, as three launches of the same shape that pass their scalars through partial sums.
-// So is the vector side of retrieval.fista's (step, clamp, restart, momentum), as two launches.
+// So is the vector side of retrieval.fista's (step, clamp, restart, momentum), as two launches,
+// and that of retrieval.primal_dual's (primal step and clamp, dual step and clamp), as two more.
 #include "common.hpp"
 #include "stage.hpp"
+#include "sphrt_pd.h"
 
 namespace sphrt {
 
@@ -528,6 +530,101 @@ __global__ __launch_bounds__(kLossThreads) void pg_momentum_kernel(
     if (blockIdx.x == 0 && threadIdx.x == 0) *j_out = j;
 }
 
+// ---- primal-dual (retrieval.primal_dual): the vector side in two launches -------------------------
+// For min F(x) + sum_ax c_ax |D_ax x|_1 over lower <= x <= upper (include/sphrt_pd.h): the
+// steps tau and sigma are read through pointers (they come from an L estimated on the device).
+// Both kernels stream their vectors once with plain loads and take the neighbours from cache;
+// index arithmetic as smooth_sum's (32-bit divisions, n < 2^31), and every neighbour index stays
+// inside the volume.  Contraction is switched off in each body, so the products that feed the
+// sums stay plain multiplies under any -ffp-contract, as sphrt_pd.h promises.
+struct PdDesc {
+    uint32_t nr, ne, na;
+    int has_r, has_e, has_a;    // the axis has edges (host: flag set and length > 1)
+    int wrap;                   // the azimuth ring is closed (and na > 1)
+};
+
+// One axis of (D^T q)[i]: + q_ax[lower neighbour] for the edge arriving at i, then - q_ax[i] for
+// the edge leaving it (coordinate c of n along the axis, element stride s).
+__device__ __forceinline__ void pd_axis_adjoint(const double* __restrict__ qa, uint32_t i,
+                                                uint32_t c, uint32_t n, uint32_t s, bool wrap,
+                                                double& S) {
+#pragma clang fp contract(off)
+    if (c > 0 || wrap) S = S + qa[c > 0 ? i - s : i + (n - 1) * s];
+    if (c + 1 < n || wrap) S = S - qa[i];
+}
+
+__global__ __launch_bounds__(kLossThreads) void pd_primal_kernel(
+    const double* __restrict__ x, const double* __restrict__ g, const double* __restrict__ q,
+    double* __restrict__ x_new, uint32_t n, PdDesc p, double c_damp,
+    const double* __restrict__ tau, double lower, double upper, double* __restrict__ part_mm) {
+#pragma clang fp contract(off)
+    const double neg_tau = -*tau;
+    const uint32_t se = p.na, sr = p.ne * p.na;
+    double mm = 0.0;
+    for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
+         i += gridDim.x * kLossThreads) {
+        const uint32_t q1 = i / p.na, a = i - q1 * p.na;
+        const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+        const double xi = x[i];
+        const double gp = fma(c_damp, xi, g[i]);
+        double S = 0.0;
+        if (p.has_r) pd_axis_adjoint(q, i, r, p.nr, sr, false, S);
+        if (p.has_e) pd_axis_adjoint(q + n, i, e, p.ne, se, false, S);
+        if (p.has_a) pd_axis_adjoint(q + 2 * (size_t)n, i, a, p.na, 1u, p.wrap != 0, S);
+        const double u = fma(neg_tau, gp + S, xi);
+        const double xn = u < lower ? lower : (u > upper ? upper : u);
+        x_new[i] = xn;
+        const double dx = xn - xi;
+        mm += dx * dx;
+    }
+    block_partial(mm, part_mm);
+}
+
+// One axis of the dual update at voxel i (xb_i = 2 x_new[i] - x_old[i]): the edge leaving i, if
+// any, takes v = fma(sigma, xb_j - xb_i, q) clamped to +-c, and its squared change goes onto t.
+__device__ __forceinline__ void pd_axis_dual(const double* __restrict__ x_new,
+                                             const double* __restrict__ x_old, double* qa,
+                                             uint32_t i, double xb_i, uint32_t c, uint32_t n,
+                                             uint32_t s, bool wrap, double sigma, double cax,
+                                             double& t) {
+#pragma clang fp contract(off)
+    if (!(c + 1 < n || wrap)) return;
+    const uint32_t j = c + 1 < n ? i + s : i - (n - 1) * s;
+    const double xb_j = fma(2.0, x_new[j], -x_old[j]);
+    const double qo = qa[i];
+    const double v = fma(sigma, xb_j - xb_i, qo);
+    const double qn = v < -cax ? -cax : (v > cax ? cax : v);
+    qa[i] = qn;
+    const double dq = qn - qo;
+    t += dq * dq;
+}
+
+// (q is read and written at the thread's own slots only: in place; not __restrict__-qualified
+// against itself, and distinct from x_new / x_old by the host's overlap check)
+__global__ __launch_bounds__(kLossThreads) void pd_dual_kernel(
+    const double* __restrict__ x_new, const double* __restrict__ x_old, double* q, uint32_t n,
+    PdDesc p, double c_r, double c_e, double c_a, const double* __restrict__ sigma,
+    double* __restrict__ part_qq) {
+#pragma clang fp contract(off)
+    const double sg = *sigma;
+    const uint32_t se = p.na, sr = p.ne * p.na;
+    double qq = 0.0;
+    for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
+         i += gridDim.x * kLossThreads) {
+        const uint32_t q1 = i / p.na, a = i - q1 * p.na;
+        const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+        const double xb = fma(2.0, x_new[i], -x_old[i]);
+        double t = 0.0;
+        if (p.has_r) pd_axis_dual(x_new, x_old, q, i, xb, r, p.nr, sr, false, sg, c_r, t);
+        if (p.has_e) pd_axis_dual(x_new, x_old, q + n, i, xb, e, p.ne, se, false, sg, c_e, t);
+        if (p.has_a)
+            pd_axis_dual(x_new, x_old, q + 2 * (size_t)n, i, xb, a, p.na, 1u, p.wrap != 0, sg,
+                         c_a, t);
+        qq += t;
+    }
+    block_partial(qq, part_qq);
+}
+
 static unsigned loss_grid(int64_t n) {
     const int64_t b = (n + kLossThreads - 1) / kLossThreads;
     return (unsigned)(b < kLossMaxBlocks ? (b > 0 ? b : 1) : kLossMaxBlocks);
@@ -826,4 +923,70 @@ extern "C" int sphrt_pg_momentum_f64(double* z, const double* x_new, const doubl
                        (hipStream_t)stream, z, x_new, x_old, n, part_gd, (int)n_part, omega,
                        n_omega, j_in, j_out);
     return check_launch("pg_momentum");
+}
+
+// The host refusals the two primal-dual entries share -> the voxel count through n (nothing is
+// dereferenced).
+static int refuse_pd(const char* me, int nr, int ne, int na, int64_t& n) {
+    if (nr < 1 || ne < 1 || na < 1)
+        return fail("%s: axis lengths (%d, %d, %d) must be >= 1", me, nr, ne, na);
+    n = (int64_t)nr * ne;                      // (< 2^62)
+    if (n < ((int64_t)1 << 31)) n *= na;
+    if (n >= ((int64_t)1 << 31))
+        return fail("%s: the volume must have fewer than 2^31 voxels", me);
+    return 0;
+}
+
+static PdDesc pd_desc(int nr, int ne, int na, int wrap_a, int has_r, int has_e, int has_a) {
+    return PdDesc{(uint32_t)nr, (uint32_t)ne, (uint32_t)na, has_r && nr > 1, has_e && ne > 1,
+                  has_a && na > 1, wrap_a && na > 1};
+}
+
+extern "C" int sphrt_pd_primal_f64(const double* x, const double* g, const double* q,
+                                   double* x_new, int nr, int ne, int na, int wrap_a, int has_r,
+                                   int has_e, int has_a, double c_damp, const double* tau,
+                                   double lower, double upper, double* part_mm, void* stream) {
+    const char* me = "sphrt_pd_primal_f64";
+    int64_t n = 0;
+    if (int e = refuse_pd(me, nr, ne, na, n)) return e;
+    if (!x || !g || !q || !x_new || !tau || !part_mm) return fail("%s: null buffer", me);
+    if (lower != lower || upper != upper || !(lower < upper))
+        return fail("%s: bounds need lower < upper, neither NaN (%g, %g)", me, lower, upper);
+    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
+    const void* buf[6] = {x, g, x_new, q, part_mm, tau};
+    const int64_t len[6] = {nb, nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
+    for (int a = 0; a < 6; ++a)
+        for (int b = a + 1; b < 6; ++b)
+            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(pd_primal_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, x, g, q, x_new, (uint32_t)n,
+                       pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a), c_damp, tau, lower, upper,
+                       part_mm);
+    return check_launch("pd_primal");
+}
+
+extern "C" int sphrt_pd_dual_f64(const double* x_new, const double* x_old, double* q, int nr,
+                                 int ne, int na, int wrap_a, int has_r, int has_e, int has_a,
+                                 double c_r, double c_e, double c_a, const double* sigma,
+                                 double* part_qq, void* stream) {
+    const char* me = "sphrt_pd_dual_f64";
+    int64_t n = 0;
+    if (int e = refuse_pd(me, nr, ne, na, n)) return e;
+    if (!x_new || !x_old || !q || !sigma || !part_qq) return fail("%s: null buffer", me);
+    for (double c : {c_r, c_e, c_a})
+        if (!(c >= 0.0) || __builtin_isinf(c))             // (a NaN fails the compare)
+            return fail("%s: the clamps c_ax must be finite and >= 0, not %g", me, c);
+    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
+    const void* buf[5] = {x_new, x_old, q, part_qq, sigma};
+    const int64_t len[5] = {nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
+    for (int a = 0; a < 5; ++a)
+        for (int b = a + 1; b < 5; ++b)
+            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(pd_dual_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, x_new, x_old, q, (uint32_t)n,
+                       pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a), c_r, c_e, c_a, sigma,
+                       part_qq);
+    return check_launch("pd_dual");
 }

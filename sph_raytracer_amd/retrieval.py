@@ -964,25 +964,32 @@ def fista(f, y, loss_fns=[SquareLoss()], x0=None, num_iterations=100, damp=0.0, 
     on the device, the whole solve enqueued without a host sync and bitwise reproducible where
     the adjoint is.  Everything else runs the same algorithm in plain torch (`_fista_generic`)."""
     sq, smooth = _cg_terms(y, loss_fns, damp, 0.0, num_iterations, who='fista')
+    bounds = _fista_args(lower, upper, lipschitz, power_iterations)
+    bar = _Bar(range(num_iterations), progress_bar)
+    run = _fista_direct if _cg_is_direct(f, y, x0) else _fista_generic
+    return run(f, y, sq, smooth, x0, num_iterations, float(damp), bounds[0], bounds[1],
+               None if lipschitz is None else float(lipschitz), power_iterations, bar)
+
+
+def _fista_args(lower, upper, lipschitz, power_iterations, who='fista'):
+    """(lower, upper) as floats, None being no bound; ValueError naming the argument that is
+    not what `fista` takes.  `primal_dual` takes the same arguments, under its own name."""
     bounds = []
     for name, v, none in (('lower', lower, -math.inf), ('upper', upper, math.inf)):
         if v is None:
             v = none
         if not _number(v) or math.isnan(v):
-            raise ValueError(f'fista needs {name} as a number (not NaN) or None, not {v!r}')
+            raise ValueError(f'{who} needs {name} as a number (not NaN) or None, not {v!r}')
         bounds.append(float(v))
     if not bounds[0] < bounds[1]:
-        raise ValueError(f'fista needs lower < upper, not lower = {lower!r}, upper = {upper!r}')
+        raise ValueError(f'{who} needs lower < upper, not lower = {lower!r}, upper = {upper!r}')
     if lipschitz is not None and (not _number(lipschitz) or not 0 < lipschitz < math.inf):
-        raise ValueError(f'fista needs a finite lipschitz > 0 (or None), not {lipschitz!r}')
+        raise ValueError(f'{who} needs a finite lipschitz > 0 (or None), not {lipschitz!r}')
     if isinstance(power_iterations, bool) or not isinstance(power_iterations, int) \
             or power_iterations < 1:
-        raise ValueError(f'fista needs power_iterations as an integer >= 1, not '
+        raise ValueError(f'{who} needs power_iterations as an integer >= 1, not '
                          f'{power_iterations!r}')
-    bar = _Bar(range(num_iterations), progress_bar)
-    run = _fista_direct if _cg_is_direct(f, y, x0) else _fista_generic
-    return run(f, y, sq, smooth, x0, num_iterations, float(damp), bounds[0], bounds[1],
-               None if lipschitz is None else float(lipschitz), power_iterations, bar)
+    return bounds
 
 
 def _fista_omega(num_iterations):
@@ -1119,3 +1126,246 @@ def _fista_direct(f, y, sq, smooth, x0, num_iterations, damp, lower, upper, lips
         mm = _kernel_sum(part_mm[:done]) if done else L.new_zeros(0)
         host = t.cat([mm, jrec[:done + 1].to(f64), L]).cpu().tolist()
     return x, y_hat, _fista_info(host[:done], host[done:2 * done + 1], host[-1])
+
+
+# ---- total variation: a primal-dual solver ---------------------------------------------------------
+
+def primal_dual(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=0.0, upper=None,
+                lipschitz=None, power_iterations=_FISTA_POWER_ITERATIONS, dual_ratio=1.0,
+                progress_bar=False):
+    """Minimise, subject to lower <= x <= upper elementwise, the total `fista` solves plus an
+    anisotropic total variation,
+
+        J(x) = lam_f * mean(w * (y - f(x))^2) + lam_s * SmoothRegularizer(kind='square')(x)
+               + damp * mean(x^2) + lam_tv * SmoothRegularizer(kind='abs')(x),
+
+    by the primal-dual iteration of Condat and Vu -> (x, f(x), info).  `loss_fns`: one SquareLoss
+    and at most one SmoothRegularizer(kind='square') by `cg`'s rules, and exactly one
+    SmoothRegularizer(kind='abs') with a scalar lam > 0 and unit masks, at least one of whose
+    axes has edges on this grid (weight > 0 and length > 1; its time_weight must be 0 unless
+    the volume is 3-D, where the class ignores it).  `lower`, `upper`, `lipschitz`,
+    `power_iterations`, `damp` and `num_iterations` as `fista` takes them; `dual_ratio`: a
+    finite number > 0.  Anything else raises ValueError naming the offender.
+
+    With grad of the smooth part N x - b (`cg`'s docstring), V = x.numel(), c_ax = lam_tv w_ax /
+    V, D the forward differences along the axes that have edges (an edge belongs to its lower
+    voxel, the azimuth wrap edge to the ring's last voxel: sphrt_smooth_reg_f64's edges), a dual
+    q of shape (3,) + x.shape that is +0.0 where there is no edge, B = 4 (number of axes with
+    edges) >= |D|^2 and L as `fista` estimates it,
+
+        tau = 1 / ((1 + dual_ratio) L),   sigma = dual_ratio L / B      (0 both when L is not > 0)
+
+    (1 / tau - sigma |D|^2 >= L > L / 2: Condat's condition).  From x_0 = clamp(x0 or
+    zeros), q_0 = 0, iteration k is
+
+        gp  = fma(c, x, N x - b),  c = 2 damp / V
+        s   = D^T q
+        u   = fma(-tau, gp + s, x);  x+ = u < lower ? lower : (u > upper ? upper : u)
+        xb  = fma(2, x+, -x)
+        q_ax <- v < -c_ax ? -c_ax : (v > c_ax ? c_ax : v),  v = fma(sigma, (D xb)_ax, q_ax)
+        MM_k = sum (x+ - x)^2;  QQ_k = sum (q+ - q)^2
+
+    info = {'primal_change': [sqrt(MM_k / MM_0)] (0.0 where MM_k is exactly 0), 'dual_change':
+    [sqrt(QQ_k)], 'lipschitz': L, 'tau', 'sigma', 'dual': q (the tensor: with x it certifies
+    optimality)}.  No tolerance, no early exit; every iterate satisfies the bounds and every
+    |q_ax| <= c_ax exactly.
+
+    The inputs `cg` runs directly (`_cg_is_direct`) run `_primal_dual_direct`: the operator's own
+    launches and two csrc/loss.hip launches per iteration (include/sphrt_pd.h), the whole solve
+    enqueued without a host sync and bitwise reproducible where the adjoint is.  Everything else
+    runs the same algorithm in plain torch (`_primal_dual_generic`)."""
+    who = 'primal_dual'
+    tvs = [fn for fn in loss_fns if type(fn) is SmoothRegularizer and fn.smooth_kind == 'abs']
+    rest = [fn for fn in loss_fns if not any(fn is v for v in tvs)]
+    sq, smooth = _cg_terms(y, rest, damp, 0.0, num_iterations, who=who)
+    if not tvs:
+        raise ValueError(f"{who} needs one SmoothRegularizer(kind='abs') among loss_fns (fista "
+                         'solves the total without it)')
+    if len(tvs) > 1:
+        raise ValueError(f"{who} solves with one SmoothRegularizer(kind='abs'), not {len(tvs)}")
+    tv = tvs[0]
+    if not tv.use_grad:
+        raise ValueError(f'{who}: SmoothRegularizer(use_grad=False) is a monitor, not a term of '
+                         'the total')
+    if not _number(tv.lam) or not 0 < tv.lam < math.inf:
+        raise ValueError(f"{who} needs a finite scalar lam > 0 on SmoothRegularizer(kind='abs'), "
+                         f'not lam = {tv.lam!r}')
+    if not _unit(tv.volume_mask):
+        raise ValueError(f"{who} does not take a volume_mask (SmoothRegularizer(kind='abs'))")
+    if not _unit(tv.projection_mask):
+        raise ValueError(f"{who}: the projection_mask of SmoothRegularizer(kind='abs') must be 1")
+    bounds = _fista_args(lower, upper, lipschitz, power_iterations, who=who)
+    if not _number(dual_ratio) or not 0 < dual_ratio < math.inf:
+        raise ValueError(f'{who} needs a finite dual_ratio > 0, not {dual_ratio!r}')
+    shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
+    if len(shape) < 3:
+        raise ValueError(f'{who} needs a volume with axes (..., r, e, a), not shape {shape}')
+    if len(shape) > 3 and tv.time_weight > 0:
+        raise ValueError(f"{who}: SmoothRegularizer(kind='abs', time_weight={tv.time_weight!r}) "
+                         'on a volume with a time axis is not built (time_weight=0 is)')
+    if not any(_pd_axes(tv, shape)):
+        raise ValueError(f"{who}: SmoothRegularizer(kind='abs', weights={tv.weights!r}) has no "
+                         f'edges on a volume of shape {shape} (an axis needs a weight > 0 and a '
+                         'length > 1)')
+    bar = _Bar(range(num_iterations), progress_bar)
+    run = _primal_dual_direct if _cg_is_direct(f, y, x0) else _primal_dual_generic
+    return run(f, y, sq, smooth, tv, x0, num_iterations, float(damp), bounds[0], bounds[1],
+               None if lipschitz is None else float(lipschitz), power_iterations,
+               float(dual_ratio), bar)
+
+
+def _pd_axes(tv, shape):
+    """[has_r, has_e, has_a]: which of the trailing axes of a volume of `shape` have edges."""
+    return [w > 0 and n > 1 for w, n in zip(tv.weights, shape[-3:])]
+
+
+def _pd_steps(L, dual_ratio, n_axes):
+    """(tau, sigma) as one-element tensors beside L: 1 / ((1 + ratio) L) and ratio L / B with
+    B = 4 n_axes; both 0 when L is not > 0 (`_fista_step`'s rule for its step)."""
+    zero = t.zeros_like(L)
+    tau = t.where(L > 0, 1.0 / ((1.0 + dual_ratio) * L), zero)
+    sigma = t.where(L > 0, (dual_ratio * L) / (4.0 * n_axes), zero)
+    return tau, sigma
+
+
+def _pd_info(mm, qq, L, tau, sigma, q):
+    """`primal_dual`'s info from MM_k and QQ_k (k = 0 .. K - 1) and the steps, on the host."""
+    mm0 = mm[0] if mm else 0.0
+    hist = [0.0 if v == 0 else math.sqrt(v / mm0) if mm0 > 0 else float('nan') for v in mm]
+    return {'primal_change': hist, 'dual_change': [math.sqrt(v) if v >= 0 else float('nan')
+                                                   for v in qq],
+            'lipschitz': L, 'tau': tau, 'sigma': sigma, 'dual': q}
+
+
+def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, upper, lipschitz,
+                         power_iterations, dual_ratio, bar):
+    """`primal_dual` in plain torch, through f(x) and f._apply_adjoint alone: the specification
+    of `_primal_dual_direct` (narrow / roll differences, sums in torch's order) and what runs on
+    the CPU.  Every scalar stays a tensor on the device: no sync inside the loop."""
+    with t.no_grad():
+        yd = y.detach()
+        x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=yd.device) if x0 is None \
+            else t.as_tensor(x0).detach().clone()
+        n_vox = x.numel()
+        c = 2 * damp / n_vox
+        normal = _normal_generic(f, yd, sq, smooth, x)
+        has, ring = _pd_axes(tv, x.shape), tv.wraps(f) and x.shape[-1] > 1
+        cax = [t.full((), tv.lam * w / n_vox, dtype=x.dtype, device=x.device) for w in tv.weights]
+        lo, hi = (t.full((), v, dtype=x.dtype, device=x.device) for v in (lower, upper))
+
+        def clamp(u, a, b):
+            return t.where(u < a, a, t.where(u > b, b, u))
+
+        def edges(v, ax):
+            """The views (lower voxels, upper voxels) of `v` along axis ax, or None for the ring
+            (every voxel has its edge: roll)."""
+            if ax == 2 and ring:
+                return None
+            n = v.shape[ax - 3]
+            return v.narrow(ax - 3, 0, n - 1), v.narrow(ax - 3, 1, n - 1)
+
+        L, _ = _fista_step(lambda v: t.add(normal(v, None), v, alpha=c), x, lipschitz,
+                           power_iterations)
+        tau, sigma = _pd_steps(L, dual_ratio, sum(has))
+        x = clamp(x, lo, hi)
+        q = x.new_zeros((3,) + tuple(x.shape))
+        mms, qqs = [], []
+        try:
+            for _ in bar:
+                gp = t.add(normal(x, yd), x, alpha=c)
+                s = t.zeros_like(x)        # D^T q: the arriving edge, then the leaving one
+                for ax in range(3):
+                    if not has[ax]:
+                        continue
+                    if edges(s, ax) is None:
+                        s += t.roll(q[ax], 1, -1)
+                        s -= q[ax]
+                    else:
+                        edges(s, ax)[1].add_(edges(q[ax], ax)[0])
+                        edges(s, ax)[0].sub_(edges(q[ax], ax)[0])
+                x_new = clamp(t.addcmul(x, gp + s, -tau), lo, hi)
+                xb = 2 * x_new - x
+                q_new = q.clone()
+                for ax in range(3):
+                    if not has[ax]:
+                        continue
+                    if edges(xb, ax) is None:
+                        v = t.addcmul(q[ax], t.roll(xb, -1, -1) - xb, sigma)
+                        q_new[ax] = clamp(v, -cax[ax], cax[ax])
+                    else:
+                        below, above = edges(xb, ax)
+                        v = t.addcmul(edges(q[ax], ax)[0], above - below, sigma)
+                        edges(q_new[ax], ax)[0].copy_(clamp(v, -cax[ax], cax[ax]))
+                mms.append(((x_new - x) ** 2).sum())
+                qqs.append(((q_new - q) ** 2).sum())
+                x, q = x_new, q_new
+        except KeyboardInterrupt:
+            pass
+        y_hat = f(x)
+        done = len(mms)
+        host = t.cat([t.stack(mms + qqs).to(t.float64) if done else L.new_zeros(0).to(t.float64),
+                      L.to(t.float64), tau.to(t.float64), sigma.to(t.float64)]).cpu().tolist()
+    return x, y_hat, _pd_info(host[:done], host[done:2 * done], *host[-3:], q)
+
+
+def _primal_dual_direct(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, upper, lipschitz,
+                        power_iterations, dual_ratio, bar):
+    """`primal_dual` on the operator's own entries (`_cg_is_direct`).  An iteration is g = N x - b
+    without the damping term (`_normal_direct` against y: over a MatrixFreeOperator one trace,
+    over an Operator its forward, residual and adjoint launches; the smooth launch with a square
+    smooth term) followed by the two launches of include/sphrt_pd.h: sphrt_pd_primal_f64 (the
+    damping term, D^T q, the step, the clamp into the other of two x buffers, partial sums of
+    MM) and sphrt_pd_dual_f64 (2 x+ - x on the fly, the dual step and clamp in place, partial
+    sums of QQ).  tau and sigma are one-element device tensors the launches read through
+    pointers — L comes from the power method in torch over the same application — so nothing is
+    read back before the loop ends; MM_k and QQ_k are then one row of partial sums each per
+    iteration (`_kernel_sum`).  Ctrl-C ends the loop after the last iteration whose dual launch
+    went out: the x returned and info['dual'] are always the pair of one iteration."""
+    from . import _lib
+    lib = _lib.load()
+    dev, f64 = f._cdev, t.float64
+    with t.no_grad(), t.cuda.device(dev):
+        x = t.zeros(tuple(f.grid.shape), dtype=f64, device=dev) if x0 is None \
+            else x0.detach().clone()
+        n_vox = x.numel()
+        nr, ne, na = x.shape
+        c = 2 * damp / n_vox
+        has = [int(h) for h in _pd_axes(tv, x.shape)]
+        ring = int(tv.wraps(f) and na > 1)
+        cax = [tv.lam * w / n_vox for w in tv.weights]
+        apply, pn = _normal_direct(f, y, sq, smooth, x)
+        L, _ = _fista_step(lambda v: t.add(apply(v), v, alpha=c), x, lipschitz, power_iterations)
+        tau, sigma = _pd_steps(L, dual_ratio, sum(has))
+        lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
+        x = t.where(x < lo, lo, t.where(x > hi, hi, x))
+        x_new = t.empty_like(x)
+        q = t.zeros((3, nr, ne, na), dtype=f64, device=dev)
+        rows = max(num_iterations, 1)
+        part_mm = t.empty((rows, pn), dtype=f64, device=dev)
+        part_qq = t.empty((rows, pn), dtype=f64, device=dev)
+        # (done: iterations whose x is current; dual_out: the iteration whose dual launch, the
+        # only writer of q, has gone out)
+        done, dual_out = 0, -1
+        try:
+            for it in bar:
+                g = apply(x, True)
+                stream = _lib.stream_of(dev)
+                _lib.check(lib.sphrt_pd_primal_f64(
+                    _lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), nr, ne, na, ring,
+                    *has, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
+                    'sphrt_pd_primal_f64')
+                _lib.check(lib.sphrt_pd_dual_f64(
+                    _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring, *has, *cax,
+                    _lib.ptr(sigma), _lib.ptr(part_qq[it]), stream), 'sphrt_pd_dual_f64')
+                dual_out = it
+                x, x_new, done = x_new, x, it + 1      # (one statement: not separable)
+        except KeyboardInterrupt:
+            # Ctrl-C inside an iteration: before its dual launch q is still the q of x (the
+            # iteration is dropped); after it, q is one step ahead, and so is x_new: finish
+            # the iteration, so that the x returned and info['dual'] belong together
+            if dual_out == done:
+                x, x_new, done = x_new, x, done + 1
+        y_hat = f(x)       # (goes out before the readback waits)
+        sums = _kernel_sum(t.cat([part_mm[:done], part_qq[:done]])) if done else L.new_zeros(0)
+        host = t.cat([sums, L, tau, sigma]).cpu().tolist()
+    return x, y_hat, _pd_info(host[:done], host[done:2 * done], *host[-3:], q)
