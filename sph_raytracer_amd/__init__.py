@@ -5,7 +5,7 @@
 from .raytracer import MatrixFreeOperator, Operator, back_project, line_integrals
 from .geometry import *  # noqa: F401,F403
 from .geometry import __all__ as _geometry_all
-from .retrieval import cg, fista, gd, primal_dual
+from .retrieval import cg, chambolle_pock, fista, gd, primal_dual
 
 __all__ = ['Operator', 'MatrixFreeOperator', 'back_project', 'line_integrals', 'gd', 'cg',
-           'fista', 'primal_dual'] + list(_geometry_all)
+           'fista', 'primal_dual', 'chambolle_pock'] + list(_geometry_all)

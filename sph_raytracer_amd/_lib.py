@@ -202,6 +202,13 @@ _PD_SIGNATURES = [
                                   c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp]),
 ]
 PD_EXPORTED = [s[0] for s in _PD_SIGNATURES]
+# and for include/sphrt_cp.h (retrieval.chambolle_pock's ray-side launch)
+_CP_SIGNATURES = [
+    ('sphrt_cp_ray_dual_f64', c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+]
+CP_EXPORTED = [s[0] for s in _CP_SIGNATURES]
+CP_SQUARE, CP_ABS, CP_HUBER, CP_POISSON = range(4)     # SPHRT_CP_* (sphrt_cp.h)
 # sphrt_exact_sort_lists methods and info fields (sphrt.h)
 SORT_SERIAL_AOS, SORT_SERIAL_SOA, SORT_WAVE1, SORT_WAVE4, SORT_NETWORK = range(5)
 SORT_INFO_FIELDS = 4
@@ -227,7 +234,7 @@ def load():
     lib.sphrt_version.argtypes = []
     if not os.environ.get('SPHRT_LIB'):   # an A/B variant may come from other sources
         _check_hash(lib.sphrt_version().decode(), LIB_PATH)
-    for name, res, args in _SIGNATURES + _PD_SIGNATURES:
+    for name, res, args in _SIGNATURES + _PD_SIGNATURES + _CP_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:

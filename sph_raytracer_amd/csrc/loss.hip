@@ -18,9 +18,11 @@
 // here too, as three launches of the same shape that pass their scalars through partial sums.
 // So is the vector side of retrieval.fista's (step, clamp, restart, momentum), as two launches,
 // and that of retrieval.primal_dual's (primal step and clamp, dual step and clamp), as two more.
+// retrieval.chambolle_pock adds the ray side: one launch for the fidelity's dual (sphrt_cp.h).
 #include "common.hpp"
 #include "stage.hpp"
 #include "sphrt_pd.h"
+#include "sphrt_cp.h"
 
 namespace sphrt {
 
@@ -625,6 +627,61 @@ __global__ __launch_bounds__(kLossThreads) void pd_dual_kernel(
     block_partial(qq, part_qq);
 }
 
+// The ray side of retrieval.chambolle_pock (include/sphrt_cp.h: the operation order of every
+// kind): p <- prox_{sigma phi*}(p + sigma (2 z_new - z_old)) in place at the thread's own slot
+// i = order[j], its copy in the adjoint's order, and the partial sums of (p+ - p)^2 and of
+// weight * rho(z_new, y) — rho op for op that of the residual kernels above.  48 bytes read and
+// 8 or 16 written per ray, coalesced but for the gathers through `order`.
+template <typename TY, int KIND>
+__global__ __launch_bounds__(kLossThreads) void cp_ray_dual_kernel(
+    const double* __restrict__ z_new, const double* __restrict__ z_old, const TY* __restrict__ y,
+    int64_t n, double par, const double* __restrict__ ray_scale,
+    const double* __restrict__ weight, const double* __restrict__ sigma,
+    const int32_t* __restrict__ order, double* p, double* __restrict__ p_adj,
+    double* __restrict__ part_pp, double* __restrict__ part_fid) {
+#pragma clang fp contract(off)
+    const double sg = *sigma;
+    double pp = 0.0, fid = 0.0;
+    for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
+         j += (int64_t)gridDim.x * kLossThreads) {
+        const int64_t i = order ? (int64_t)order[j] : j;
+        const double zn = z_new[i], m = (double)y[i], s = ray_scale[i], po = p[i];
+        const double zb = fma(2.0, zn, -z_old[i]);
+        const double a = fma(sg, zb, po);
+        const double t = fma(-sg, m, a);
+        const double r = zn - m;
+        double pn, h;
+        if constexpr (KIND == SPHRT_CP_SQUARE) {
+            pn = t / (1.0 + sg / (2.0 * s));
+            h = r * r;
+        } else if constexpr (KIND == SPHRT_CP_ABS) {
+            pn = t < -s ? -s : (t > s ? s : t);
+            h = __builtin_fabs(r);
+        } else if constexpr (KIND == SPHRT_CP_HUBER) {
+            const double u = t / (1.0 + sg / s), b = s * par;
+            pn = u < -b ? -b : (u > b ? b : u);
+            const double z = __builtin_fabs(r);
+            h = z < par ? (0.5 * z) * z : par * (z - 0.5 * par);
+        } else {
+            const double a1 = fma(sg, par, a);
+            const double d = a1 - s, e = a1 + s;
+            const double disc = fma((4.0 * sg) * s, m, d * d);
+            const double v = 0.5 * (e - sqrt(disc));
+            pn = v > s ? s : v;
+            const double lg = m * log(zn + par);
+            h = zn - lg;
+        }
+        if (s == 0.0) pn = 0.0;
+        p[i] = pn;
+        if (order) p_adj[j] = pn;
+        const double dp = pn - po;
+        pp += dp * dp;
+        const double wh = weight[i] * h;
+        fid += wh;
+    }
+    block_partial2(pp, fid, part_pp, part_fid);
+}
+
 static unsigned loss_grid(int64_t n) {
     const int64_t b = (n + kLossThreads - 1) / kLossThreads;
     return (unsigned)(b < kLossMaxBlocks ? (b > 0 ? b : 1) : kLossMaxBlocks);
@@ -989,4 +1046,66 @@ extern "C" int sphrt_pd_dual_f64(const double* x_new, const double* x_old, doubl
                        pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a), c_r, c_e, c_a, sigma,
                        part_qq);
     return check_launch("pd_dual");
+}
+
+template <typename TY>
+static void cp_launch(int kind, unsigned grid, hipStream_t st, const double* z_new,
+                      const double* z_old, const TY* y, int64_t n, double par,
+                      const double* ray_scale, const double* weight, const double* sigma,
+                      const int32_t* order, double* p, double* p_adj, double* part_pp,
+                      double* part_fid) {
+#define SPHRT_CP_CASE(K)                                                                      \
+    case K:                                                                                   \
+        hipLaunchKernelGGL((cp_ray_dual_kernel<TY, K>), dim3(grid), dim3(kLossThreads), 0, st, \
+                           z_new, z_old, y, n, par, ray_scale, weight, sigma, order, p, p_adj, \
+                           part_pp, part_fid);                                                \
+        break;
+    switch (kind) {
+        SPHRT_CP_CASE(SPHRT_CP_SQUARE)
+        SPHRT_CP_CASE(SPHRT_CP_ABS)
+        SPHRT_CP_CASE(SPHRT_CP_HUBER)
+        SPHRT_CP_CASE(SPHRT_CP_POISSON)
+    }
+#undef SPHRT_CP_CASE
+}
+
+extern "C" int sphrt_cp_ray_dual_f64(const double* z_new, const double* z_old, const void* y,
+                                     int y_is_f64, int64_t n, int kind, double delta_or_eps,
+                                     const double* ray_scale, const double* weight,
+                                     const double* sigma, const int32_t* order, double* p,
+                                     double* p_adj, double* part_pp, double* part_fid,
+                                     void* stream) {
+    const char* me = "sphrt_cp_ray_dual_f64";
+    if (n <= 0) return fail("%s: empty measurement (n %lld)", me, (long long)n);
+    if (kind < SPHRT_CP_SQUARE || kind > SPHRT_CP_POISSON)
+        return fail("%s: unknown kind %d (SPHRT_CP_SQUARE .. SPHRT_CP_POISSON)", me, kind);
+    double par = 0.0;
+    if (kind == SPHRT_CP_HUBER) {
+        if (int e = refuse_robust(SPHRT_RESID_HUBER, delta_or_eps, par)) return e;
+    } else if (kind == SPHRT_CP_POISSON) {
+        if (int e = refuse_poisson(delta_or_eps)) return e;
+        par = delta_or_eps;
+    }
+    if (!z_new || !z_old || !y || !ray_scale || !weight || !sigma || !p || !part_pp || !part_fid)
+        return fail("%s: null buffer", me);
+    if ((order == nullptr) != (p_adj == nullptr))
+        return fail("%s: null buffer (order and p_adj go together)", me);
+    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
+    const void* buf[11] = {p, p_adj, part_pp, part_fid, z_new, z_old, y, ray_scale, weight,
+                           sigma, order};
+    const int64_t len[11] = {nb, nb, pb, pb, nb, nb, y_is_f64 ? nb : nb / 2, nb, nb,
+                             (int64_t)sizeof(double), n * (int64_t)sizeof(int32_t)};
+    for (int a = 0; a < 4; ++a)                    // (an output against everything after it)
+        for (int b = a + 1; b < 11; ++b)
+            if (buf[a] && buf[b] && overlap(buf[a], len[a], buf[b], len[b]))
+                return fail("%s: aliased buffers", me);
+    StreamGuard guard(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (y_is_f64)
+        cp_launch(kind, loss_grid(n), st, z_new, z_old, (const double*)y, n, par, ray_scale,
+                  weight, sigma, order, p, p_adj, part_pp, part_fid);
+    else
+        cp_launch(kind, loss_grid(n), st, z_new, z_old, (const float*)y, n, par, ray_scale, weight,
+                  sigma, order, p, p_adj, part_pp, part_fid);
+    return check_launch("cp_ray_dual");
 }

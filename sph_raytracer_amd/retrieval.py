@@ -763,6 +763,35 @@ def _kernel_sum(part):
     return ((((0.0 + v[:, 0]) + v[:, 1]) + v[:, 2]) + v[:, 3]).reshape(part.shape[:-1])
 
 
+def _stored_loop_setup(f, yd, w_res, s_res):
+    """What a direct loop over a stored Operator arranges once, as _gd_direct does: the loop's
+    forward descriptor (or None: f(d) itself), the adjoint's input order, the measurements and
+    the per-ray factors (None: unweighted) in the order the loop's forward writes — trace
+    positions when the descriptor's rows can be pointed at them, else geometry rays, and then
+    `res_order` gathers the adjoint's input.  (The brick-staged forward packs d itself.)
+    -> (loop_desc, order, res_order, y_res, w_res, s_res, keep): keep = (the staged pair, the
+    trace-position lists), either None when not in use, for the caller to hold."""
+    f64, n_meas = t.float64, yd.numel()
+    staged = f._stage_for_loop(f64)
+    if staged is not None and f._csr['n'] != n_meas:
+        staged = None
+    order = f._adjoint_trace_order()
+    if order is not None and order.numel() != n_meas:
+        order = None
+    loop_desc = staged[0] if staged is not None else None
+    y_res, res_order, keep_rows = yd.reshape(-1), order, None
+    if order is not None:
+        sd = loop_desc if loop_desc is not None else f._loop_descriptor(f64)
+        keep_rows = f._trace_position_rows(sd) if sd is not None else None
+        if keep_rows is not None:
+            loop_desc = sd
+            y_res, res_order = y_res.index_select(0, f._ray_id_long()), None
+            if w_res is not None:
+                w_res, s_res = (v.index_select(0, f._ray_id_long())
+                                for v in (w_res, s_res))
+    return loop_desc, order, res_order, y_res, w_res, s_res, (staged, keep_rows)
+
+
 def _normal_direct(f, y, sq, smooth, x):
     """apply(d) / apply(d, against_y=True) = A^T(s (A d - m)) + G d, m = 0 or y, on the operator's
     own entries (`_cg_is_direct`), for contiguous float64 volumes like `x` on the operator's GPU:
@@ -804,25 +833,8 @@ def _normal_direct(f, y, sq, smooth, x):
                            weighted=weighted)
             return h_buf
     else:
-        # the loop's forward descriptor, the adjoint's input order and the measurements in
-        # that order, as _gd_direct sets them up (the brick-staged forward packs d itself)
-        staged = f._stage_for_loop(f64)
-        if staged is not None and f._csr['n'] != n_meas:
-            staged = None
-        order = f._adjoint_trace_order()
-        if order is not None and order.numel() != n_meas:
-            order = None
-        loop_desc = staged[0] if staged is not None else None
-        y_res, res_order, keep_rows = yd.reshape(-1), order, None
-        if order is not None:
-            sd = loop_desc if loop_desc is not None else f._loop_descriptor(f64)
-            keep_rows = f._trace_position_rows(sd) if sd is not None else None
-            if keep_rows is not None:
-                loop_desc = sd
-                y_res, res_order = y_res.index_select(0, f._ray_id_long()), None
-                if w_res is not None:
-                    w_res, s_res = (v.index_select(0, f._ray_id_long())
-                                    for v in (w_res, s_res))
+        loop_desc, order, res_order, y_res, w_res, s_res, _keep = _stored_loop_setup(
+            f, yd, w_res, s_res)
         rs_buf = t.empty(n_meas, dtype=f64, device=dev)
 
         def normal(d, against_y):
@@ -1237,6 +1249,54 @@ def _pd_info(mm, qq, L, tau, sigma, q):
             'lipschitz': L, 'tau': tau, 'sigma': sigma, 'dual': q}
 
 
+def _tv_generic(tv, f, x):
+    """The TV term's two maps in plain torch (narrow / roll differences) over volumes like `x`,
+    for `_primal_dual_generic` and `_chambolle_pock_generic` -> (has, adjoint, dual): which axes
+    have edges; adjoint(q) = D^T q; dual(q, xb, sigma) = the clamped dual step, a new tensor."""
+    n_vox = x.numel()
+    has, ring = _pd_axes(tv, x.shape), tv.wraps(f) and x.shape[-1] > 1
+    cax = [t.full((), tv.lam * w / n_vox, dtype=x.dtype, device=x.device) for w in tv.weights]
+
+    def clamp(u, a, b):
+        return t.where(u < a, a, t.where(u > b, b, u))
+
+    def edges(v, ax):
+        """The views (lower voxels, upper voxels) of `v` along axis ax, or None for the ring
+        (every voxel has its edge: roll)."""
+        if ax == 2 and ring:
+            return None
+        n = v.shape[ax - 3]
+        return v.narrow(ax - 3, 0, n - 1), v.narrow(ax - 3, 1, n - 1)
+
+    def adjoint(q):
+        s = t.zeros_like(q[0])     # D^T q: the arriving edge, then the leaving one
+        for ax in range(3):
+            if not has[ax]:
+                continue
+            if edges(s, ax) is None:
+                s += t.roll(q[ax], 1, -1)
+                s -= q[ax]
+            else:
+                edges(s, ax)[1].add_(edges(q[ax], ax)[0])
+                edges(s, ax)[0].sub_(edges(q[ax], ax)[0])
+        return s
+
+    def dual(q, xb, sigma):
+        q_new = q.clone()
+        for ax in range(3):
+            if not has[ax]:
+                continue
+            if edges(xb, ax) is None:
+                v = t.addcmul(q[ax], t.roll(xb, -1, -1) - xb, sigma)
+                q_new[ax] = clamp(v, -cax[ax], cax[ax])
+            else:
+                below, above = edges(xb, ax)
+                v = t.addcmul(edges(q[ax], ax)[0], above - below, sigma)
+                edges(q_new[ax], ax)[0].copy_(clamp(v, -cax[ax], cax[ax]))
+        return q_new
+    return has, adjoint, dual
+
+
 def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, upper, lipschitz,
                          power_iterations, dual_ratio, bar):
     """`primal_dual` in plain torch, through f(x) and f._apply_adjoint alone: the specification
@@ -1249,20 +1309,11 @@ def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, 
         n_vox = x.numel()
         c = 2 * damp / n_vox
         normal = _normal_generic(f, yd, sq, smooth, x)
-        has, ring = _pd_axes(tv, x.shape), tv.wraps(f) and x.shape[-1] > 1
-        cax = [t.full((), tv.lam * w / n_vox, dtype=x.dtype, device=x.device) for w in tv.weights]
+        has, tv_adjoint, tv_dual = _tv_generic(tv, f, x)
         lo, hi = (t.full((), v, dtype=x.dtype, device=x.device) for v in (lower, upper))
 
         def clamp(u, a, b):
             return t.where(u < a, a, t.where(u > b, b, u))
-
-        def edges(v, ax):
-            """The views (lower voxels, upper voxels) of `v` along axis ax, or None for the ring
-            (every voxel has its edge: roll)."""
-            if ax == 2 and ring:
-                return None
-            n = v.shape[ax - 3]
-            return v.narrow(ax - 3, 0, n - 1), v.narrow(ax - 3, 1, n - 1)
 
         L, _ = _fista_step(lambda v: t.add(normal(v, None), v, alpha=c), x, lipschitz,
                            power_iterations)
@@ -1273,29 +1324,8 @@ def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, 
         try:
             for _ in bar:
                 gp = t.add(normal(x, yd), x, alpha=c)
-                s = t.zeros_like(x)        # D^T q: the arriving edge, then the leaving one
-                for ax in range(3):
-                    if not has[ax]:
-                        continue
-                    if edges(s, ax) is None:
-                        s += t.roll(q[ax], 1, -1)
-                        s -= q[ax]
-                    else:
-                        edges(s, ax)[1].add_(edges(q[ax], ax)[0])
-                        edges(s, ax)[0].sub_(edges(q[ax], ax)[0])
-                x_new = clamp(t.addcmul(x, gp + s, -tau), lo, hi)
-                xb = 2 * x_new - x
-                q_new = q.clone()
-                for ax in range(3):
-                    if not has[ax]:
-                        continue
-                    if edges(xb, ax) is None:
-                        v = t.addcmul(q[ax], t.roll(xb, -1, -1) - xb, sigma)
-                        q_new[ax] = clamp(v, -cax[ax], cax[ax])
-                    else:
-                        below, above = edges(xb, ax)
-                        v = t.addcmul(edges(q[ax], ax)[0], above - below, sigma)
-                        edges(q_new[ax], ax)[0].copy_(clamp(v, -cax[ax], cax[ax]))
+                x_new = clamp(t.addcmul(x, gp + tv_adjoint(q), -tau), lo, hi)
+                q_new = tv_dual(q, 2 * x_new - x, sigma)
                 mms.append(((x_new - x) ** 2).sum())
                 qqs.append(((q_new - q) ** 2).sum())
                 x, q = x_new, q_new
@@ -1369,3 +1399,435 @@ def _primal_dual_direct(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, u
         sums = _kernel_sum(t.cat([part_mm[:done], part_qq[:done]])) if done else L.new_zeros(0)
         host = t.cat([sums, L, tau, sigma]).cpu().tolist()
     return x, y_hat, _pd_info(host[:done], host[done:2 * done], *host[-3:], q)
+
+
+# ---- robust and Poisson fidelity with TV and bounds: Chambolle-Pock ---------------------------------
+
+# sigma = dual_ratio * (lam / M) / |K|: the ratio tools/cp_study.py chose (DESIGN §5,
+# "Chambolle-Pock solver").
+_CP_DUAL_RATIO = 1.0
+
+
+def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=0.0, upper=None,
+                   norm=None, power_iterations=_FISTA_POWER_ITERATIONS,
+                   dual_ratio=_CP_DUAL_RATIO, progress_bar=False):
+    """Minimise, subject to lower <= x <= upper elementwise,
+
+        J(x) = sum_i phi_i((A x)_i) + damp * mean(x^2) + lam_tv * SmoothRegularizer(kind='abs')(x)
+
+    by the primal-dual hybrid gradient of Chambolle and Pock in Condat's form, the fidelity term
+    dualised as `primal_dual` dualises the TV term -> (x, f(x), info).  No Lipschitz constant of
+    the fidelity is needed, only the proximal map of its conjugate, which is closed-form and
+    elementwise over the rays for all four fidelity classes.
+
+    `loss_fns`: exactly one fidelity term, of exact type SquareLoss, AbsLoss, HuberLoss or
+    PoissonLoss (a finite scalar lam > 0, unit volume_mask, a projection_mask that is 1 or a tensor
+    `gd`'s direct loop would weigh the residual with; its entries must be >= 0, which is not
+    checked — reading the mask back would synchronise the host — and a negative entry turns that
+    ray's clamp interval inside out: the result is then meaningless), and at most one
+    SmoothRegularizer(kind='abs') under `primal_dual`'s rules for it (on a volume with a time axis
+    its time_weight must be 0).  `lower`, `upper`, `power_iterations`, `damp` and `num_iterations`
+    as `fista` takes them; `norm`: the caller's own |A|^2, a finite number > 0, as `lipschitz=` is
+    for `fista`; `dual_ratio`: a finite number > 0.  Anything else raises ValueError naming the
+    offender, before the operator is touched.
+
+    With M = y.numel(), V = x.numel(), s_i = lam w_i / M and z = A x, phi_i(z) is what the loss
+    classes compute: s (z - y)^2, s |z - y|, s huber_delta(z - y) (torch's), s (z - y log(z +
+    eps)).  `y` is not checked for sign: a negative count under PoissonLoss gives what IEEE gives
+    (a negative discriminant: NaN).  A ray that misses the grid has (A x)_i = 0 whatever x is;
+    under PoissonLoss a positive count on it (background) leaves its dual heading for -s_i y_i /
+    eps, which no iteration count reaches: x is unaffected, but info['ray_dual'] and a duality
+    gap formed from it mean nothing on such rays.  Give them weight 0 in the projection_mask
+    (then p_i = +0.0 and the ray leaves the total).  State: x, the ray dual p (the shape of y), the TV dual q (as
+    in `primal_dual`) and z.  With c = 2 damp / V, iteration k is
+
+        g  = A^T p
+        x+ = clamp(fma(-tau, fma(c, x, g) + D^T q, x))             (sphrt_pd_primal_f64)
+        q  <- clamp(fma(sigma, D(2 x+ - x), q), +-c_ax)            (sphrt_pd_dual_f64; with TV)
+        z+ = A x+
+        p  <- prox_{sigma phi*}(a),  a = fma(sigma, fma(2, z+, -z), p)   (sphrt_cp_ray_dual_f64)
+
+    and with t = a - sigma y the prox is: abs clamp(t, +-s); huber clamp(t / (1 + sigma / s),
+    +-s delta); square t / (1 + sigma / (2 s)); poisson, with a' = a + sigma eps,
+    min(s, ((a' + s) - sqrt((a' - s)^2 + 4 sigma s y)) / 2); a ray with s_i = 0 always gets +0.0.
+
+    Steps: Kn^2 = L_A + B, L_A an upper estimate of |A|^2 (`fista`'s power method and margin on
+    v -> A^T(A v), or `norm`), B = 4 (number of TV axes with edges), 0 without TV; with sbar =
+    lam / M, sigma = dual_ratio sbar / Kn and 1 / tau = sigma Kn^2 + c (Condat's condition
+    1 / tau - sigma |K|^2 >= c / 2; both 0 when Kn is not > 0).
+
+    info = {'primal_change': [sqrt(MM_k / MM_ref)] (as `primal_dual`, but MM_ref is the first MM_k
+    that is not zero: from p_0 = 0 the first step moves x only through the damping term),
+    'dual_change': [sqrt(QQ_k)] (zeros without TV), 'ray_dual_change': [sqrt(sum (p+ - p)^2)], 'fidelity': [sum_i phi_i(z+_i)],
+    'norm': L_A, 'tau', 'sigma', 'dual': q or None without TV, 'ray_dual': p}.  Every iterate
+    satisfies the bounds exactly, and so do the duals: |q_ax| <= c_ax, |p_i| <= s_i (abs),
+    |p_i| <= s_i delta (huber), p_i <= s_i (poisson), each clamp storing the bound's own bits.
+    There is no tolerance and no early exit.
+
+    The inputs `cg` runs directly (`_cg_is_direct`) run `_chambolle_pock_direct`: the operator's
+    own launches and three csrc/loss.hip launches per iteration (two without TV), the whole solve
+    enqueued without a host sync and bitwise reproducible where the adjoint is.  Over a
+    MatrixFreeOperator an iteration is two traces (the forward and the back-projection: the
+    prox sits between them), not `primal_dual`'s one.  Everything else — CPU tensors, dynamic
+    operators, other dtypes, a non-contiguous x0 — runs the same algorithm in plain torch
+    (`_chambolle_pock_generic`)."""
+    who = 'chambolle_pock'
+    fid, tv = _cp_terms(y, loss_fns, damp, num_iterations, who)
+    bounds = _fista_args(lower, upper, None, power_iterations, who=who)
+    if norm is not None and (not _number(norm) or not 0 < norm < math.inf):
+        raise ValueError(f'{who} needs a finite norm > 0 (or None), not {norm!r}')
+    if not _number(dual_ratio) or not 0 < dual_ratio < math.inf:
+        raise ValueError(f'{who} needs a finite dual_ratio > 0, not {dual_ratio!r}')
+    if tv is not None:
+        shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
+        if len(shape) < 3:
+            raise ValueError(f'{who} needs a volume with axes (..., r, e, a), not shape {shape}')
+        if len(shape) > 3 and tv.time_weight > 0:
+            raise ValueError(f"{who}: SmoothRegularizer(kind='abs', time_weight="
+                             f'{tv.time_weight!r}) on a volume with a time axis is not built '
+                             '(time_weight=0 is)')
+        if not any(_pd_axes(tv, shape)):
+            raise ValueError(f"{who}: SmoothRegularizer(kind='abs', weights={tv.weights!r}) has "
+                             f'no edges on a volume of shape {shape} (an axis needs a weight > 0 '
+                             'and a length > 1)')
+    bar = _Bar(range(num_iterations), progress_bar)
+    run = _chambolle_pock_direct if _cg_is_direct(f, y, x0) else _chambolle_pock_generic
+    return run(f, y, fid, tv, x0, num_iterations, float(damp), bounds[0], bounds[1],
+               None if norm is None else float(norm), power_iterations, float(dual_ratio), bar)
+
+
+def _cp_terms(y, loss_fns, damp, num_iterations, who):
+    """(the fidelity term, the SmoothRegularizer(kind='abs') or None) of a total `chambolle_pock`
+    solves; ValueError naming what it does not, worded as `_cg_terms` words it."""
+    if not isinstance(y, t.Tensor):
+        raise ValueError(f'{who} needs measurements y as a tensor, not {type(y).__name__}')
+    if not _number(damp) or not 0 <= damp < float('inf'):
+        raise ValueError(f'{who} needs a finite damp >= 0, not {damp!r}')
+    if isinstance(num_iterations, bool) or not isinstance(num_iterations, int) \
+            or num_iterations < 0:
+        raise ValueError(f'{who} needs num_iterations as an integer >= 0, not {num_iterations!r}')
+    fid = tv = None
+    for fn in loss_fns:
+        name = type(fn).__name__
+        if type(fn) in _FIDELITY:
+            if fid is not None:
+                raise ValueError(f'{who} solves for one fidelity term, not two')
+            fid = fn
+        elif type(fn) is SmoothRegularizer:
+            if fn.smooth_kind != 'abs':
+                raise ValueError(f"{who} takes a smooth term as total variation only: "
+                                 f"SmoothRegularizer(kind={fn.smooth_kind!r}) is not built "
+                                 "(kind='abs' is)")
+            if tv is not None:
+                raise ValueError(f"{who} solves with at most one SmoothRegularizer(kind='abs'), "
+                                 'not two')
+            tv = fn
+        else:
+            raise ValueError(f'{who} needs a total of one SquareLoss, AbsLoss, HuberLoss or '
+                             f"PoissonLoss and at most one SmoothRegularizer(kind='abs'): {name} "
+                             'is neither (gd takes it)')
+        if not fn.use_grad:
+            raise ValueError(f'{who}: {name}(use_grad=False) is a monitor, not a term of the total')
+        if not _number(fn.lam) or not 0 < fn.lam < math.inf:
+            raise ValueError(f'{who} needs a finite scalar lam > 0, not {name}.lam = {fn.lam!r}')
+        if not _unit(fn.volume_mask):
+            raise ValueError(f'{who} does not take a volume_mask ({name})')
+        if not _unit(fn.projection_mask) and not (fn is fid and _ray_mask(fn.projection_mask, y)):
+            raise ValueError(f'{who}: the projection_mask of {name} must be 1' + (
+                ' or a bool / float32 / float64 tensor on the device of y that broadcasts to '
+                'its shape' if fn is fid else ''))
+    if fid is None:
+        raise ValueError(f'{who} needs one SquareLoss, AbsLoss, HuberLoss or PoissonLoss among '
+                         'loss_fns')
+    return fid, tv
+
+
+def _cp_kind(fid):
+    """(kind, delta or eps) of a fidelity term as sphrt_cp_ray_dual_f64 takes them."""
+    from . import _lib
+    if type(fid) is AbsLoss:
+        return _lib.CP_ABS, 0.0
+    if type(fid) is HuberLoss:
+        return _lib.CP_HUBER, float(fid.delta)
+    if type(fid) is PoissonLoss:
+        return _lib.CP_POISSON, float(fid.eps)
+    return _lib.CP_SQUARE, 0.0
+
+
+def _cp_prox(kind, par, a, sigma, s, m):
+    """prox_{sigma phi*}(a) per ray in plain torch, the operations of include/sphrt_cp.h in its
+    order (torch's multiply-adds are not fused): `s` the rays' factors, `m` the measurements,
+    `sigma` a one-element tensor, `par` the Huber delta or the Poisson eps."""
+    tt = t.addcmul(a, m, -sigma)
+    if kind == 0:
+        pn = tt / (1.0 + sigma / (2.0 * s))
+    elif kind == 1:
+        pn = t.where(tt < -s, -s, t.where(tt > s, s, tt))
+    elif kind == 2:
+        u, b = tt / (1.0 + sigma / s), s * par
+        pn = t.where(u < -b, -b, t.where(u > b, b, u))
+    else:
+        a1 = a + sigma * par
+        d, e = a1 - s, a1 + s
+        v = 0.5 * (e - t.sqrt(d * d + ((4.0 * sigma) * s) * m))
+        pn = t.where(v > s, s, v)
+    return t.where(s == 0, t.zeros_like(pn), pn)
+
+
+def _cp_rho(kind, par, z, m):
+    """rho(z, m) per ray, as the loss classes form it."""
+    if kind == 0:
+        return (z - m) ** 2
+    if kind == 1:
+        return (z - m).abs()
+    if kind == 2:
+        return t.nn.functional.huber_loss(z, m, reduction='none', delta=par)
+    return z - m * t.log(z + par)
+
+
+def _cp_steps(LA, n_axes, s_bar, c, dual_ratio):
+    """(tau, sigma) as one-element tensors beside L_A: Kn^2 = L_A + 4 n_axes, sigma = ratio
+    sbar / Kn, tau = 1 / (sigma Kn^2 + c); both 0 when Kn is not > 0."""
+    kn2 = LA + 4.0 * n_axes
+    kn, zero = t.sqrt(kn2), t.zeros_like(LA)
+    ok = kn > 0
+    sigma = t.where(ok, (dual_ratio * s_bar) / kn, zero)
+    tau = t.where(ok, 1.0 / (sigma * kn2 + c), zero)
+    return tau, sigma
+
+
+def _cp_info(mm, qq, pp, fid, LA, tau, sigma, q, p):
+    """`chambolle_pock`'s info from the per-iteration sums and the steps, on the host."""
+    info = _pd_info(mm, qq, LA, tau, sigma, q)
+    # (p_0 = 0: without damping the first step does not move x, so the reference is the first
+    # MM_k that is not zero)
+    mm0 = next((v for v in mm if v > 0), 0.0)
+    info['primal_change'] = [0.0 if v == 0 else math.sqrt(v / mm0) if mm0 > 0 else float('nan')
+                             for v in mm]
+    info['norm'] = info.pop('lipschitz')
+    info['ray_dual_change'] = [math.sqrt(v) if v >= 0 else float('nan') for v in pp]
+    info['fidelity'] = fid
+    info['ray_dual'] = p
+    return info
+
+
+def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, upper, norm,
+                            power_iterations, dual_ratio, bar):
+    """`chambolle_pock` in plain torch, through f(x) and f._apply_adjoint alone: the
+    specification of `_chambolle_pock_direct` (sums in torch's order) and what runs on the CPU.
+    Every scalar stays a tensor on the device: no sync inside the loop."""
+    with t.no_grad():
+        yd = y.detach()
+        x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=yd.device) if x0 is None \
+            else t.as_tensor(x0).detach().clone()
+        dshape, dtype, dev = tuple(x.shape), x.dtype, x.device
+        pdt = t.promote_types(yd.dtype, dtype)
+        m = yd.to(pdt)
+        n_vox, n_meas = x.numel(), yd.numel()
+        c = 2 * damp / n_vox
+        kind, par = _cp_kind(fid)
+        s_bar = fid.lam / n_meas
+        w = None if _unit(fid.projection_mask) else \
+            fid.projection_mask.detach().to(pdt).expand(yd.shape)
+        s = t.full_like(m, s_bar) if w is None else s_bar * w
+        lo, hi = (t.full((), v, dtype=dtype, device=dev) for v in (lower, upper))
+        has, tv_adjoint, tv_dual = _tv_generic(tv, f, x) if tv is not None else ([], None, None)
+        # |A|^2: v -> A^T(A v) is `_normal_generic` of a SquareLoss whose factor 2 lam / M is 1
+        ata = _normal_generic(f, yd, SquareLoss(lam=n_meas / 2), None, x)
+        LA, _ = _fista_step(lambda v: ata(v, None), x, norm, power_iterations)
+        tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+        x = t.where(x < lo, lo, t.where(x > hi, hi, x))
+        q = x.new_zeros((3,) + dshape) if tv is not None else None
+        z = f(x)
+        p = t.zeros_like(m)
+        mms, qqs, pps, fids, done = [], [], [], [], 0
+        try:
+            for _ in bar:
+                g = f._apply_adjoint(p, dshape, dtype, dev)
+                gp = t.add(g, x, alpha=c)
+                if tv is not None:
+                    gp = gp + tv_adjoint(q)
+                u = t.addcmul(x, gp, -tau)
+                x_new = t.where(u < lo, lo, t.where(u > hi, hi, u))
+                q_new = tv_dual(q, 2 * x_new - x, sigma) if tv is not None else None
+                z_new = f(x_new)
+                p_new = _cp_prox(kind, par, t.addcmul(p, 2 * z_new - z, sigma), sigma, s, m)
+                rho = _cp_rho(kind, par, z_new.to(pdt), m)
+                fids.append(s_bar * (rho if w is None else w * rho).sum())
+                mms.append(((x_new - x) ** 2).sum())
+                pps.append(((p_new - p) ** 2).sum())
+                if tv is not None:
+                    qqs.append(((q_new - q) ** 2).sum())
+                x, z, p, q, done = x_new, z_new, p_new, q_new, done + 1
+        except KeyboardInterrupt:
+            pass
+        for sums in (mms, qqs, pps, fids):      # (Ctrl-C: the sums of an iteration not kept)
+            del sums[done:]
+        y_hat = f(x)
+        if tv is None:
+            qqs = [LA.new_zeros(()) for _ in range(done)]
+        sums = t.stack(mms + qqs + pps + fids).to(t.float64) if done \
+            else LA.new_zeros(0).to(t.float64)
+        host = t.cat([sums, LA.to(t.float64), tau.to(t.float64),
+                      sigma.to(t.float64)]).cpu().tolist()
+    return x, y_hat, _cp_info(*(host[k * done:(k + 1) * done] for k in range(4)), *host[-3:], q, p)
+
+
+def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper, norm,
+                           power_iterations, dual_ratio, bar):
+    """`chambolle_pock` on the operator's own entries (`_cg_is_direct`).  An iteration is
+    g = A^T p — over an Operator its adjoint on the dual in the adjoint's order, over a
+    MatrixFreeOperator the atomic back-projection, or with `deterministic` set
+    `_backproject_fixed_into` — then sphrt_pd_primal_f64 (the damping term, D^T q, the step, the
+    clamp into the other of two x buffers, partial sums of MM), with a TV term sphrt_pd_dual_f64,
+    the forward z+ = A x+ into the other of two z buffers (the loop's forward, or
+    `_forward_into`: a second trace) and sphrt_cp_ray_dual_f64 (include/sphrt_cp.h: the ray
+    dual's prox in place, its copy in the adjoint's order, partial sums of its change and of the
+    fidelity).  Measurements, weights and the ray order over an Operator are arranged as
+    `_normal_direct` arranges them (`_stored_loop_setup`); p lives in the order the loop's
+    forward writes and info['ray_dual'] is put back into geometry order at the end.  tau and
+    sigma are one-element device tensors the launches read through pointers — L_A comes from the
+    power method in torch over `_normal_direct`'s application of A^T A — so nothing is read back
+    before the loop ends; the histories are then rows of partial sums (`_kernel_sum`).  Ctrl-C
+    inside an iteration drops it if nothing was written in place yet, and otherwise sends out
+    its remaining steps, so that the x, q and p returned are those of one iteration — with the
+    care `_primal_dual_direct` takes and its one gap: an interrupt that lands between the return
+    of an in-place launch and the `stage += 1` after it is not seen as that launch (counting
+    first instead would lose the launch itself to an interrupt during its argument list, a
+    longer stretch of bytecode)."""
+    from . import _lib
+    from .raytracer import MatrixFreeOperator
+    lib = _lib.load()
+    dev, f64 = f._cdev, t.float64
+    fused = isinstance(f, MatrixFreeOperator)
+    with t.no_grad(), t.cuda.device(dev):
+        x = t.zeros(tuple(f.grid.shape), dtype=f64, device=dev) if x0 is None \
+            else x0.detach().clone()
+        dshape = tuple(x.shape)
+        n_vox = x.numel()
+        nr, ne, na = x.shape
+        c = 2 * damp / n_vox
+        yd = y.detach().contiguous()
+        n_meas = yd.numel()
+        kind, par = _cp_kind(fid)
+        s_bar = fid.lam / n_meas
+        if isinstance(fid.projection_mask, t.Tensor):
+            w_ray = fid.projection_mask.detach().to(f64).expand(yd.shape).contiguous().reshape(-1)
+            s_ray = s_bar * w_ray
+        else:
+            w_ray = t.ones(n_meas, dtype=f64, device=dev)
+            s_ray = t.full((n_meas,), s_bar, dtype=f64, device=dev)
+        if tv is not None:
+            has = [int(h) for h in _pd_axes(tv, x.shape)]
+            ring = int(tv.wraps(f) and na > 1)
+            cax = [tv.lam * w / n_vox for w in tv.weights]
+        else:
+            has, ring, cax = [0, 0, 0], 0, [0.0, 0.0, 0.0]
+        # |A|^2 on the operator's own launches: `_normal_direct` of a SquareLoss whose factor
+        # 2 lam / M is 1 applies v -> A^T(A v)
+        ata, pn = _normal_direct(f, y, SquareLoss(lam=n_meas / 2), None, x)
+        LA, _ = _fista_step(ata, x, norm, power_iterations)
+        del ata
+        tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+        ps = lib.sphrt_loss_partials(n_meas)
+        y_ray, order, res_order, loop_desc, positions, keep = yd.reshape(-1), None, None, None, \
+            False, None
+        if fused:
+            fixed = f._fixed_buffers() if f.deterministic else None
+            g_buf = t.empty_like(x)
+        else:
+            loop_desc, order, res_order, y_ray, w_ray, s_ray, keep = _stored_loop_setup(
+                f, yd, w_ray, s_ray)
+            positions = keep[1] is not None
+        y_f64 = int(y_ray.dtype == f64)
+        z, z_new = (t.empty(n_meas, dtype=f64, device=dev) for _ in range(2))
+        p = t.zeros(n_meas, dtype=f64, device=dev)
+        p_adj = t.zeros(n_meas, dtype=f64, device=dev) if res_order is not None else None
+
+        def forward(d, out):
+            """A d in the loop's ray order -> the buffer that holds it."""
+            if fused:
+                f._forward_into(d, out)
+            elif loop_desc is not None:
+                f._forward_staged(d, out, loop_desc)
+            else:
+                return f(d).reshape(-1)
+            return out
+
+        def adjoint():
+            """A^T p -> a buffer the next application may overwrite."""
+            if not fused:
+                return f._apply_adjoint((p if p_adj is None else p_adj).view(yd.shape), dshape,
+                                        f64, dev, trace_order=order is not None)
+            if fixed is None:
+                return f._apply_adjoint(p.view(yd.shape), dshape, f64, dev)
+            f._backproject_fixed_into(p, g_buf, fixed)
+            return g_buf
+
+        lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
+        x = t.where(x < lo, lo, t.where(x > hi, hi, x))
+        x_new = t.empty_like(x)
+        # (without TV the primal launch never reads q, has_* being 0, but refuses a null or an
+        # overlapping one: the buffer stays, untouched)
+        q = t.zeros((3, nr, ne, na), dtype=f64, device=dev)
+        rows = max(num_iterations, 1)
+        part_mm = t.empty((rows, pn), dtype=f64, device=dev)
+        part_qq = t.zeros((rows, pn), dtype=f64, device=dev)
+        part_pp = t.empty((rows, ps), dtype=f64, device=dev)
+        part_fid = t.empty((rows, ps), dtype=f64, device=dev)
+        z = forward(x, z)
+        # (done: iterations whose x, z, q and p are current; stage: how many of the next
+        # iteration's four steps have gone out — the second and the fourth write q and p in place)
+        done, stage, zn = 0, 0, None
+
+        def advance(it):
+            """The steps of iteration `it` that have not gone out yet, in order."""
+            nonlocal stage, zn
+            while stage < 4:
+                stream = _lib.stream_of(dev)
+                if stage == 0:
+                    g = adjoint()
+                    _lib.check(lib.sphrt_pd_primal_f64(
+                        _lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), nr, ne, na, ring,
+                        *has, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
+                        'sphrt_pd_primal_f64')
+                elif stage == 1:
+                    if tv is not None:
+                        _lib.check(lib.sphrt_pd_dual_f64(
+                            _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring, *has,
+                            *cax, _lib.ptr(sigma), _lib.ptr(part_qq[it]), stream),
+                            'sphrt_pd_dual_f64')
+                elif stage == 2:
+                    zn = forward(x_new, z_new)
+                else:
+                    _lib.check(lib.sphrt_cp_ray_dual_f64(
+                        _lib.ptr(zn), _lib.ptr(z), _lib.ptr(y_ray), y_f64, n_meas, kind, par,
+                        _lib.ptr(s_ray), _lib.ptr(w_ray), _lib.ptr(sigma), _lib.ptr(res_order),
+                        _lib.ptr(p), _lib.ptr(p_adj), _lib.ptr(part_pp[it]),
+                        _lib.ptr(part_fid[it]), stream), 'sphrt_cp_ray_dual_f64')
+                stage += 1
+
+        try:
+            for it in bar:
+                advance(it)
+                x, x_new, z, z_new, done, stage = x_new, x, zn, z, it + 1, 0   # (one statement)
+        except KeyboardInterrupt:
+            # Ctrl-C inside an iteration: before its TV-dual launch (without TV: its ray-dual
+            # launch) nothing has been written in place, and the iteration is dropped; after it,
+            # q (or p) is one step ahead of x: the remaining steps go out, so that the x, q and p
+            # returned belong to one iteration
+            if done < num_iterations and stage >= (2 if tv is not None else 4):
+                advance(done)
+                x, x_new, z, z_new, done, stage = x_new, x, zn, z, done + 1, 0
+        y_hat = f(x)       # (goes out before the readback waits)
+        if done:
+            sums = t.cat([_kernel_sum(t.cat([part_mm[:done], part_qq[:done]])),
+                          _kernel_sum(t.cat([part_pp[:done], part_fid[:done]]))])
+        else:
+            sums = LA.new_zeros(0)
+        host = t.cat([sums, LA, tau, sigma]).cpu().tolist()
+        if positions:      # (trace positions back to geometry rays)
+            p = t.empty_like(p).index_copy_(0, f._ray_id_long(), p)
+        fids = [s_bar * v for v in host[3 * done:4 * done]]
+    return x, y_hat, _cp_info(host[:done], host[done:2 * done], host[2 * done:3 * done], fids,
+                              *host[-3:], q if tv is not None else None, p.view(yd.shape))
