@@ -209,6 +209,17 @@ _CP_SIGNATURES = [
 ]
 CP_EXPORTED = [s[0] for s in _CP_SIGNATURES]
 CP_SQUARE, CP_ABS, CP_HUBER, CP_POISSON = range(4)     # SPHRT_CP_* (sphrt_cp.h)
+# and for include/sphrt_dp.h (chambolle_pock's diagonal preconditioning: the primal step and the
+# ray dual with a step per element, and the launch that forms the steps)
+_DP_SIGNATURES = [
+    ('sphrt_dp_primal_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_dbl, c_vp, c_dbl, c_dbl, c_vp, c_vp]),
+    ('sphrt_dp_ray_dual_f64', c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ('sphrt_dp_steps_f64', c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp]),
+]
+DP_EXPORTED = [s[0] for s in _DP_SIGNATURES]
 # sphrt_exact_sort_lists methods and info fields (sphrt.h)
 SORT_SERIAL_AOS, SORT_SERIAL_SOA, SORT_WAVE1, SORT_WAVE4, SORT_NETWORK = range(5)
 SORT_INFO_FIELDS = 4
@@ -234,7 +245,7 @@ def load():
     lib.sphrt_version.argtypes = []
     if not os.environ.get('SPHRT_LIB'):   # an A/B variant may come from other sources
         _check_hash(lib.sphrt_version().decode(), LIB_PATH)
-    for name, res, args in _SIGNATURES + _PD_SIGNATURES + _CP_SIGNATURES:
+    for name, res, args in _SIGNATURES + _PD_SIGNATURES + _CP_SIGNATURES + _DP_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -43,7 +43,8 @@ _HASH_RE = re.compile(rb'sph_raytracer_amd [^\x00]*? src ([0-9a-f]{16})')
 def _hash(files, flags):
     h = hashlib.sha256()
     for name, path in [(f, os.path.join(CSRC, f)) for f in sorted(files)] + \
-            [(hdr, os.path.join(ROOT, 'include', hdr)) for hdr in ('sphrt.h', 'sphrt_pd.h', 'sphrt_cp.h')]:
+            [(hdr, os.path.join(ROOT, 'include', hdr))
+             for hdr in ('sphrt.h', 'sphrt_pd.h', 'sphrt_cp.h', 'sphrt_dp.h')]:
         with open(path, 'rb') as fh:
             data = fh.read()
         h.update(name.encode() + b'\0' + str(len(data)).encode() + b'\0' + data)

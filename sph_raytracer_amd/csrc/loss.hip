@@ -18,11 +18,14 @@
 // here too, as three launches of the same shape that pass their scalars through partial sums.
 // So is the vector side of retrieval.fista's (step, clamp, restart, momentum), as two launches,
 // and that of retrieval.primal_dual's (primal step and clamp, dual step and clamp), as two more.
-// retrieval.chambolle_pock adds the ray side: one launch for the fidelity's dual (sphrt_cp.h).
+// retrieval.chambolle_pock adds the ray side: one launch for the fidelity's dual (sphrt_cp.h),
+// and its diagonal preconditioning the same two with a step per element and the launch that forms
+// those steps (sphrt_dp.h).
 #include "common.hpp"
 #include "stage.hpp"
 #include "sphrt_pd.h"
 #include "sphrt_cp.h"
+#include "sphrt_dp.h"
 
 namespace sphrt {
 
@@ -555,12 +558,14 @@ __device__ __forceinline__ void pd_axis_adjoint(const double* __restrict__ qa, u
     if (c + 1 < n || wrap) S = S - qa[i];
 }
 
+// (PER_VOXEL: tau holds n steps, one per voxel — sphrt_dp_primal_f64 — instead of one)
+template <bool PER_VOXEL>
 __global__ __launch_bounds__(kLossThreads) void pd_primal_kernel(
     const double* __restrict__ x, const double* __restrict__ g, const double* __restrict__ q,
     double* __restrict__ x_new, uint32_t n, PdDesc p, double c_damp,
     const double* __restrict__ tau, double lower, double upper, double* __restrict__ part_mm) {
 #pragma clang fp contract(off)
-    const double neg_tau = -*tau;
+    const double neg_tau0 = PER_VOXEL ? 0.0 : -*tau;
     const uint32_t se = p.na, sr = p.ne * p.na;
     double mm = 0.0;
     for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
@@ -573,6 +578,7 @@ __global__ __launch_bounds__(kLossThreads) void pd_primal_kernel(
         if (p.has_r) pd_axis_adjoint(q, i, r, p.nr, sr, false, S);
         if (p.has_e) pd_axis_adjoint(q + n, i, e, p.ne, se, false, S);
         if (p.has_a) pd_axis_adjoint(q + 2 * (size_t)n, i, a, p.na, 1u, p.wrap != 0, S);
+        const double neg_tau = PER_VOXEL ? -tau[i] : neg_tau0;
         const double u = fma(neg_tau, gp + S, xi);
         const double xn = u < lower ? lower : (u > upper ? upper : u);
         x_new[i] = xn;
@@ -631,8 +637,9 @@ __global__ __launch_bounds__(kLossThreads) void pd_dual_kernel(
 // kind): p <- prox_{sigma phi*}(p + sigma (2 z_new - z_old)) in place at the thread's own slot
 // i = order[j], its copy in the adjoint's order, and the partial sums of (p+ - p)^2 and of
 // weight * rho(z_new, y) — rho op for op that of the residual kernels above.  48 bytes read and
-// 8 or 16 written per ray, coalesced but for the gathers through `order`.
-template <typename TY, int KIND>
+// 8 or 16 written per ray, coalesced but for the gathers through `order`.  PER_RAY: sigma holds
+// n steps, indexed as ray_scale is (sphrt_dp_ray_dual_f64), instead of one.
+template <typename TY, int KIND, bool PER_RAY>
 __global__ __launch_bounds__(kLossThreads) void cp_ray_dual_kernel(
     const double* __restrict__ z_new, const double* __restrict__ z_old, const TY* __restrict__ y,
     int64_t n, double par, const double* __restrict__ ray_scale,
@@ -640,12 +647,13 @@ __global__ __launch_bounds__(kLossThreads) void cp_ray_dual_kernel(
     const int32_t* __restrict__ order, double* p, double* __restrict__ p_adj,
     double* __restrict__ part_pp, double* __restrict__ part_fid) {
 #pragma clang fp contract(off)
-    const double sg = *sigma;
+    const double sg0 = PER_RAY ? 0.0 : *sigma;
     double pp = 0.0, fid = 0.0;
     for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
          j += (int64_t)gridDim.x * kLossThreads) {
         const int64_t i = order ? (int64_t)order[j] : j;
         const double zn = z_new[i], m = (double)y[i], s = ray_scale[i], po = p[i];
+        const double sg = PER_RAY ? sigma[i] : sg0;
         const double zb = fma(2.0, zn, -z_old[i]);
         const double a = fma(sg, zb, po);
         const double t = fma(-sg, m, a);
@@ -680,6 +688,34 @@ __global__ __launch_bounds__(kLossThreads) void cp_ray_dual_kernel(
         fid += wh;
     }
     block_partial2(pp, fid, part_pp, part_fid);
+}
+
+// The steps of the diagonally preconditioned iteration (include/sphrt_dp.h): tau per voxel from
+// the column sums and the voxel's edge count — index arithmetic as pd_primal_kernel's, no memory
+// — and sigma per ray from the row sums, in one launch over the longer of the two.
+__global__ __launch_bounds__(kLossThreads) void dp_steps_kernel(
+    const double* __restrict__ col, const double* __restrict__ row, uint32_t n_vox,
+    uint32_t n_ray, PdDesc p, double rho, double c, const int32_t* __restrict__ order,
+    double* __restrict__ tau, double* __restrict__ sigma) {
+#pragma clang fp contract(off)
+    const uint32_t n = n_vox > n_ray ? n_vox : n_ray;
+    for (uint32_t j = blockIdx.x * kLossThreads + threadIdx.x; j < n;
+         j += gridDim.x * kLossThreads) {
+        if (j < n_vox) {
+            const uint32_t q1 = j / p.na, a = j - q1 * p.na;
+            const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+            int deg = 0;
+            if (p.has_r) deg += (r > 0) + (r + 1 < p.nr);
+            if (p.has_e) deg += (e > 0) + (e + 1 < p.ne);
+            if (p.has_a) deg += p.wrap ? 2 : (a > 0) + (a + 1 < p.na);
+            const double d = fma(rho, col[j] + (double)deg, c);
+            tau[j] = d > 0.0 ? 1.0 / d : 0.0;
+        }
+        if (j < n_ray) {
+            const double r = row[order ? (uint32_t)order[j] : j];
+            sigma[j] = r > 0.0 ? rho / r : 0.0;
+        }
+    }
 }
 
 static unsigned loss_grid(int64_t n) {
@@ -999,11 +1035,11 @@ static PdDesc pd_desc(int nr, int ne, int na, int wrap_a, int has_r, int has_e, 
                   has_a && na > 1, wrap_a && na > 1};
 }
 
-extern "C" int sphrt_pd_primal_f64(const double* x, const double* g, const double* q,
-                                   double* x_new, int nr, int ne, int na, int wrap_a, int has_r,
-                                   int has_e, int has_a, double c_damp, const double* tau,
-                                   double lower, double upper, double* part_mm, void* stream) {
-    const char* me = "sphrt_pd_primal_f64";
+// sphrt_pd_primal_f64 and sphrt_dp_primal_f64: one step behind `tau`, or one per voxel.
+static int pd_primal_entry(const char* me, bool per_voxel, const double* x, const double* g,
+                           const double* q, double* x_new, int nr, int ne, int na, int wrap_a,
+                           int has_r, int has_e, int has_a, double c_damp, const double* tau,
+                           double lower, double upper, double* part_mm, void* stream) {
     int64_t n = 0;
     if (int e = refuse_pd(me, nr, ne, na, n)) return e;
     if (!x || !g || !q || !x_new || !tau || !part_mm) return fail("%s: null buffer", me);
@@ -1011,16 +1047,37 @@ extern "C" int sphrt_pd_primal_f64(const double* x, const double* g, const doubl
         return fail("%s: bounds need lower < upper, neither NaN (%g, %g)", me, lower, upper);
     const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
     const void* buf[6] = {x, g, x_new, q, part_mm, tau};
-    const int64_t len[6] = {nb, nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
+    const int64_t len[6] = {nb, nb, nb, 3 * nb, pb, per_voxel ? nb : (int64_t)sizeof(double)};
     for (int a = 0; a < 6; ++a)
         for (int b = a + 1; b < 6; ++b)
             if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
     StreamGuard guard(stream);
-    hipLaunchKernelGGL(pd_primal_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                       (hipStream_t)stream, x, g, q, x_new, (uint32_t)n,
-                       pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a), c_damp, tau, lower, upper,
-                       part_mm);
-    return check_launch("pd_primal");
+    const PdDesc desc = pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a);
+    if (per_voxel)
+        hipLaunchKernelGGL(pd_primal_kernel<true>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                           (hipStream_t)stream, x, g, q, x_new, (uint32_t)n, desc, c_damp, tau,
+                           lower, upper, part_mm);
+    else
+        hipLaunchKernelGGL(pd_primal_kernel<false>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                           (hipStream_t)stream, x, g, q, x_new, (uint32_t)n, desc, c_damp, tau,
+                           lower, upper, part_mm);
+    return check_launch(per_voxel ? "dp_primal" : "pd_primal");
+}
+
+extern "C" int sphrt_pd_primal_f64(const double* x, const double* g, const double* q,
+                                   double* x_new, int nr, int ne, int na, int wrap_a, int has_r,
+                                   int has_e, int has_a, double c_damp, const double* tau,
+                                   double lower, double upper, double* part_mm, void* stream) {
+    return pd_primal_entry("sphrt_pd_primal_f64", false, x, g, q, x_new, nr, ne, na, wrap_a, has_r,
+                           has_e, has_a, c_damp, tau, lower, upper, part_mm, stream);
+}
+
+extern "C" int sphrt_dp_primal_f64(const double* x, const double* g, const double* q,
+                                   double* x_new, int nr, int ne, int na, int wrap_a, int has_r,
+                                   int has_e, int has_a, double c_damp, const double* tau,
+                                   double lower, double upper, double* part_mm, void* stream) {
+    return pd_primal_entry("sphrt_dp_primal_f64", true, x, g, q, x_new, nr, ne, na, wrap_a, has_r,
+                           has_e, has_a, c_damp, tau, lower, upper, part_mm, stream);
 }
 
 extern "C" int sphrt_pd_dual_f64(const double* x_new, const double* x_old, double* q, int nr,
@@ -1048,7 +1105,7 @@ extern "C" int sphrt_pd_dual_f64(const double* x_new, const double* x_old, doubl
     return check_launch("pd_dual");
 }
 
-template <typename TY>
+template <typename TY, bool PER_RAY>
 static void cp_launch(int kind, unsigned grid, hipStream_t st, const double* z_new,
                       const double* z_old, const TY* y, int64_t n, double par,
                       const double* ray_scale, const double* weight, const double* sigma,
@@ -1056,9 +1113,9 @@ static void cp_launch(int kind, unsigned grid, hipStream_t st, const double* z_n
                       double* part_fid) {
 #define SPHRT_CP_CASE(K)                                                                      \
     case K:                                                                                   \
-        hipLaunchKernelGGL((cp_ray_dual_kernel<TY, K>), dim3(grid), dim3(kLossThreads), 0, st, \
-                           z_new, z_old, y, n, par, ray_scale, weight, sigma, order, p, p_adj, \
-                           part_pp, part_fid);                                                \
+        hipLaunchKernelGGL((cp_ray_dual_kernel<TY, K, PER_RAY>), dim3(grid),                  \
+                           dim3(kLossThreads), 0, st, z_new, z_old, y, n, par, ray_scale,     \
+                           weight, sigma, order, p, p_adj, part_pp, part_fid);                \
         break;
     switch (kind) {
         SPHRT_CP_CASE(SPHRT_CP_SQUARE)
@@ -1069,13 +1126,13 @@ static void cp_launch(int kind, unsigned grid, hipStream_t st, const double* z_n
 #undef SPHRT_CP_CASE
 }
 
-extern "C" int sphrt_cp_ray_dual_f64(const double* z_new, const double* z_old, const void* y,
-                                     int y_is_f64, int64_t n, int kind, double delta_or_eps,
-                                     const double* ray_scale, const double* weight,
-                                     const double* sigma, const int32_t* order, double* p,
-                                     double* p_adj, double* part_pp, double* part_fid,
-                                     void* stream) {
-    const char* me = "sphrt_cp_ray_dual_f64";
+// sphrt_cp_ray_dual_f64 and sphrt_dp_ray_dual_f64: one step behind `sigma`, or one per ray.
+template <bool PER_RAY>
+static int cp_ray_dual_entry(const char* me, const double* z_new, const double* z_old,
+                             const void* y, int y_is_f64, int64_t n, int kind,
+                             double delta_or_eps, const double* ray_scale, const double* weight,
+                             const double* sigma, const int32_t* order, double* p, double* p_adj,
+                             double* part_pp, double* part_fid, void* stream) {
     if (n <= 0) return fail("%s: empty measurement (n %lld)", me, (long long)n);
     if (kind < SPHRT_CP_SQUARE || kind > SPHRT_CP_POISSON)
         return fail("%s: unknown kind %d (SPHRT_CP_SQUARE .. SPHRT_CP_POISSON)", me, kind);
@@ -1094,7 +1151,8 @@ extern "C" int sphrt_cp_ray_dual_f64(const double* z_new, const double* z_old, c
     const void* buf[11] = {p, p_adj, part_pp, part_fid, z_new, z_old, y, ray_scale, weight,
                            sigma, order};
     const int64_t len[11] = {nb, nb, pb, pb, nb, nb, y_is_f64 ? nb : nb / 2, nb, nb,
-                             (int64_t)sizeof(double), n * (int64_t)sizeof(int32_t)};
+                             PER_RAY ? nb : (int64_t)sizeof(double),
+                             n * (int64_t)sizeof(int32_t)};
     for (int a = 0; a < 4; ++a)                    // (an output against everything after it)
         for (int b = a + 1; b < 11; ++b)
             if (buf[a] && buf[b] && overlap(buf[a], len[a], buf[b], len[b]))
@@ -1102,10 +1160,62 @@ extern "C" int sphrt_cp_ray_dual_f64(const double* z_new, const double* z_old, c
     StreamGuard guard(stream);
     hipStream_t st = (hipStream_t)stream;
     if (y_is_f64)
-        cp_launch(kind, loss_grid(n), st, z_new, z_old, (const double*)y, n, par, ray_scale,
-                  weight, sigma, order, p, p_adj, part_pp, part_fid);
+        cp_launch<double, PER_RAY>(kind, loss_grid(n), st, z_new, z_old, (const double*)y, n, par,
+                                   ray_scale, weight, sigma, order, p, p_adj, part_pp, part_fid);
     else
-        cp_launch(kind, loss_grid(n), st, z_new, z_old, (const float*)y, n, par, ray_scale, weight,
-                  sigma, order, p, p_adj, part_pp, part_fid);
-    return check_launch("cp_ray_dual");
+        cp_launch<float, PER_RAY>(kind, loss_grid(n), st, z_new, z_old, (const float*)y, n, par,
+                                  ray_scale, weight, sigma, order, p, p_adj, part_pp, part_fid);
+    return check_launch(PER_RAY ? "dp_ray_dual" : "cp_ray_dual");
+}
+
+extern "C" int sphrt_cp_ray_dual_f64(const double* z_new, const double* z_old, const void* y,
+                                     int y_is_f64, int64_t n, int kind, double delta_or_eps,
+                                     const double* ray_scale, const double* weight,
+                                     const double* sigma, const int32_t* order, double* p,
+                                     double* p_adj, double* part_pp, double* part_fid,
+                                     void* stream) {
+    return cp_ray_dual_entry<false>("sphrt_cp_ray_dual_f64", z_new, z_old, y, y_is_f64, n, kind,
+                                    delta_or_eps, ray_scale, weight, sigma, order, p, p_adj,
+                                    part_pp, part_fid, stream);
+}
+
+extern "C" int sphrt_dp_ray_dual_f64(const double* z_new, const double* z_old, const void* y,
+                                     int y_is_f64, int64_t n, int kind, double delta_or_eps,
+                                     const double* ray_scale, const double* weight,
+                                     const double* sigma, const int32_t* order, double* p,
+                                     double* p_adj, double* part_pp, double* part_fid,
+                                     void* stream) {
+    return cp_ray_dual_entry<true>("sphrt_dp_ray_dual_f64", z_new, z_old, y, y_is_f64, n, kind,
+                                   delta_or_eps, ray_scale, weight, sigma, order, p, p_adj,
+                                   part_pp, part_fid, stream);
+}
+
+extern "C" int sphrt_dp_steps_f64(const double* col, const double* row, int64_t n_ray, int nr,
+                                  int ne, int na, int wrap_a, int has_r, int has_e, int has_a,
+                                  double rho, double c, const int32_t* order, double* tau,
+                                  double* sigma, void* stream) {
+    const char* me = "sphrt_dp_steps_f64";
+    int64_t n_vox = 0;
+    if (int e = refuse_pd(me, nr, ne, na, n_vox)) return e;
+    if (n_ray < 1 || n_ray >= ((int64_t)1 << 31))
+        return fail("%s: n_ray %lld, the measurement must have 1 .. 2^31 - 1 rays", me,
+                    (long long)n_ray);
+    if (!(rho > 0.0) || __builtin_isinf(rho))                   // (a NaN fails the compare)
+        return fail("%s: rho must be finite and > 0, not %g", me, rho);
+    if (!(c >= 0.0) || __builtin_isinf(c))
+        return fail("%s: c must be finite and >= 0, not %g", me, c);
+    if (!col || !row || !tau || !sigma) return fail("%s: null buffer", me);
+    const int64_t vb = n_vox * (int64_t)sizeof(double), rb = n_ray * (int64_t)sizeof(double);
+    const void* buf[5] = {tau, sigma, col, row, order};
+    const int64_t len[5] = {vb, rb, vb, rb, n_ray * (int64_t)sizeof(int32_t)};
+    for (int a = 0; a < 2; ++a)                    // (an output against everything after it)
+        for (int b = a + 1; b < 5; ++b)
+            if (buf[b] && overlap(buf[a], len[a], buf[b], len[b]))
+                return fail("%s: aliased buffers", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(dp_steps_kernel, dim3(loss_grid(n_vox > n_ray ? n_vox : n_ray)),
+                       dim3(kLossThreads), 0, (hipStream_t)stream, col, row, (uint32_t)n_vox,
+                       (uint32_t)n_ray, pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a), rho, c,
+                       order, tau, sigma);
+    return check_launch("dp_steps");
 }

@@ -1410,7 +1410,7 @@ _CP_DUAL_RATIO = 1.0
 
 def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=0.0, upper=None,
                    norm=None, power_iterations=_FISTA_POWER_ITERATIONS,
-                   dual_ratio=_CP_DUAL_RATIO, progress_bar=False):
+                   dual_ratio=_CP_DUAL_RATIO, progress_bar=False, precondition=None):
     """Minimise, subject to lower <= x <= upper elementwise,
 
         J(x) = sum_i phi_i((A x)_i) + damp * mean(x^2) + lam_tv * SmoothRegularizer(kind='abs')(x)
@@ -1464,6 +1464,28 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
     |p_i| <= s_i delta (huber), p_i <= s_i (poisson), each clamp storing the bound's own bits.
     There is no tolerance and no early exit.
 
+    `precondition`: None (the scalar steps above) or 'diagonal': the steps of Pock and Chambolle
+    (2011), Lemma 2 with alpha = 1, for K = [A; D], one per voxel and one per ray.  A >= 0
+    entrywise, so |K|'s sums are plain sums: row_i = (A 1)_i and col_j = (A^T 1)_j (one forward and
+    one adjoint of ones: no power method, `power_iterations` is ignored and a given `norm` raises
+    ValueError), deg_j the number of TV edges at voxel j (0 .. 6; every edge row of |D| sums to
+    2).  With rho = dual_ratio sbar:
+
+        sigma_i = rho / row_i          (+0.0 where row_i is not > 0: the ray misses the grid and
+                                        its dual never moves)
+        sigma_tv = rho / 2
+        tau_j = 1 / fma(rho, col_j + deg_j, c)    (+0.0 where that is not > 0: no ray, no edge
+                                                   and no damping act on the voxel; it stays put)
+
+    and the iteration above runs with tau_j, sigma_tv and sigma_i in place of tau, sigma (TV) and
+    sigma (rays): sphrt_dp_primal_f64, sphrt_pd_dual_f64, sphrt_dp_ray_dual_f64
+    (include/sphrt_dp.h).  With T = diag(tau), S = diag(sigma_i, sigma_tv), the lemma gives
+    |S^(1/2) K T^(1/2)| <= 1 for every rho (rho cancels), and, beyond it, T^-1 - K^T S K >= c I:
+    Condat's condition with the damping term's Lipschitz constant c.  info['tau'] is then a tensor
+    of x's shape, info['sigma'] one of y's shape (geometry order), info['sigma_tv'] a float and
+    info['norm'] None; the histories keep their meaning.  Whether it pays depends on the problem:
+    README and DESIGN section 8 record the measurement.
+
     The inputs `cg` runs directly (`_cg_is_direct`) run `_chambolle_pock_direct`: the operator's
     own launches and three csrc/loss.hip launches per iteration (two without TV), the whole solve
     enqueued without a host sync and bitwise reproducible where the adjoint is.  Over a
@@ -1478,6 +1500,12 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
         raise ValueError(f'{who} needs a finite norm > 0 (or None), not {norm!r}')
     if not _number(dual_ratio) or not 0 < dual_ratio < math.inf:
         raise ValueError(f'{who} needs a finite dual_ratio > 0, not {dual_ratio!r}')
+    if precondition is not None and not (isinstance(precondition, str)
+                                         and precondition == 'diagonal'):
+        raise ValueError(f"{who} needs precondition None or 'diagonal', not {precondition!r}")
+    if precondition is not None and norm is not None:
+        raise ValueError(f"{who}: precondition='diagonal' takes its steps from the operator's row "
+                         f'and column sums, not from a norm (norm={norm!r})')
     if tv is not None:
         shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
         if len(shape) < 3:
@@ -1493,7 +1521,8 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
     bar = _Bar(range(num_iterations), progress_bar)
     run = _chambolle_pock_direct if _cg_is_direct(f, y, x0) else _chambolle_pock_generic
     return run(f, y, fid, tv, x0, num_iterations, float(damp), bounds[0], bounds[1],
-               None if norm is None else float(norm), power_iterations, float(dual_ratio), bar)
+               None if norm is None else float(norm), power_iterations, float(dual_ratio), bar,
+               diagonal=precondition is not None)
 
 
 def _cp_terms(y, loss_fns, damp, num_iterations, who):
@@ -1611,8 +1640,39 @@ def _cp_info(mm, qq, pp, fid, LA, tau, sigma, q, p):
     return info
 
 
+def _dp_degree(has, ring, x):
+    """deg_j, the number of TV edges at each voxel of the trailing three axes of `x` (has: which
+    axes have edges; ring: the azimuth ring is closed) -> a tensor of that shape, 0 .. 6."""
+    deg = t.zeros(tuple(x.shape[-3:]), dtype=x.dtype, device=x.device)
+    for ax in range(3):
+        if not has[ax]:
+            continue
+        if ax == 2 and ring:
+            deg += 2
+        else:
+            n = deg.shape[ax]
+            deg.narrow(ax, 0, n - 1).add_(1)       # the edge leaving the voxel
+            deg.narrow(ax, 1, n - 1).add_(1)       # the edge arriving at it
+    return deg
+
+
+def _dp_steps(row, col, deg, rho, c):
+    """(tau like col, sigma like row) of the diagonal preconditioning in plain torch:
+    1 / (rho (col + deg) + c) and rho / row, +0.0 where a denominator is not > 0."""
+    d = rho * (col + deg) + c
+    tau = t.where(d > 0, 1.0 / d, t.zeros_like(d))
+    sigma = t.where(row > 0, rho / row, t.zeros_like(row))
+    return tau, sigma
+
+
+def _dp_info(info, tau, sigma, sigma_tv):
+    """`chambolle_pock`'s info with the steps of the diagonal preconditioning."""
+    info.update(norm=None, tau=tau, sigma=sigma, sigma_tv=sigma_tv)
+    return info
+
+
 def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, upper, norm,
-                            power_iterations, dual_ratio, bar):
+                            power_iterations, dual_ratio, bar, diagonal=False):
     """`chambolle_pock` in plain torch, through f(x) and f._apply_adjoint alone: the
     specification of `_chambolle_pock_direct` (sums in torch's order) and what runs on the CPU.
     Every scalar stays a tensor on the device: no sync inside the loop."""
@@ -1632,10 +1692,21 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
         s = t.full_like(m, s_bar) if w is None else s_bar * w
         lo, hi = (t.full((), v, dtype=dtype, device=dev) for v in (lower, upper))
         has, tv_adjoint, tv_dual = _tv_generic(tv, f, x) if tv is not None else ([], None, None)
-        # |A|^2: v -> A^T(A v) is `_normal_generic` of a SquareLoss whose factor 2 lam / M is 1
-        ata = _normal_generic(f, yd, SquareLoss(lam=n_meas / 2), None, x)
-        LA, _ = _fista_step(lambda v: ata(v, None), x, norm, power_iterations)
-        tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+        if diagonal:
+            # row and column sums of A >= 0: one forward and one adjoint of ones
+            rho_s = dual_ratio * s_bar
+            row = f(t.ones_like(x)).to(pdt)
+            col = f._apply_adjoint(t.ones_like(m), dshape, dtype, dev)
+            deg = _dp_degree(has, tv.wraps(f) and dshape[-1] > 1, x) if tv is not None else 0.0
+            tau, sigma = _dp_steps(row, col, deg, rho_s, c)
+            sigma_tv = t.full((), rho_s / 2, dtype=dtype, device=dev)
+            LA = t.zeros(1, dtype=dtype, device=dev)
+        else:
+            # |A|^2: v -> A^T(A v) is `_normal_generic` of a SquareLoss whose factor 2 lam / M is 1
+            ata = _normal_generic(f, yd, SquareLoss(lam=n_meas / 2), None, x)
+            LA, _ = _fista_step(lambda v: ata(v, None), x, norm, power_iterations)
+            tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+            sigma_tv = sigma
         x = t.where(x < lo, lo, t.where(x > hi, hi, x))
         q = x.new_zeros((3,) + dshape) if tv is not None else None
         z = f(x)
@@ -1649,7 +1720,7 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
                     gp = gp + tv_adjoint(q)
                 u = t.addcmul(x, gp, -tau)
                 x_new = t.where(u < lo, lo, t.where(u > hi, hi, u))
-                q_new = tv_dual(q, 2 * x_new - x, sigma) if tv is not None else None
+                q_new = tv_dual(q, 2 * x_new - x, sigma_tv) if tv is not None else None
                 z_new = f(x_new)
                 p_new = _cp_prox(kind, par, t.addcmul(p, 2 * z_new - z, sigma), sigma, s, m)
                 rho = _cp_rho(kind, par, z_new.to(pdt), m)
@@ -1668,13 +1739,18 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
             qqs = [LA.new_zeros(()) for _ in range(done)]
         sums = t.stack(mms + qqs + pps + fids).to(t.float64) if done \
             else LA.new_zeros(0).to(t.float64)
+        if diagonal:
+            host = sums.cpu().tolist()
+            return x, y_hat, _dp_info(
+                _cp_info(*(host[k * done:(k + 1) * done] for k in range(4)), None, None, None, q,
+                         p), tau, sigma, float(sigma_tv))
         host = t.cat([sums, LA.to(t.float64), tau.to(t.float64),
                       sigma.to(t.float64)]).cpu().tolist()
     return x, y_hat, _cp_info(*(host[k * done:(k + 1) * done] for k in range(4)), *host[-3:], q, p)
 
 
 def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper, norm,
-                           power_iterations, dual_ratio, bar):
+                           power_iterations, dual_ratio, bar, diagonal=False):
     """`chambolle_pock` on the operator's own entries (`_cg_is_direct`).  An iteration is
     g = A^T p — over an Operator its adjoint on the dual in the adjoint's order, over a
     MatrixFreeOperator the atomic back-projection, or with `deterministic` set
@@ -1694,7 +1770,16 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
     care `_primal_dual_direct` takes and its one gap: an interrupt that lands between the return
     of an in-place launch and the `stage += 1` after it is not seen as that launch (counting
     first instead would lose the launch itself to an interrupt during its argument list, a
-    longer stretch of bytecode)."""
+    longer stretch of bytecode).
+
+    `diagonal` (precondition='diagonal'): no power method; row = A 1 (geometry order) and
+    col = A^T 1 come from one forward and one adjoint of ones on the same launches, and one
+    sphrt_dp_steps_f64 launch (include/sphrt_dp.h) writes tau per voxel and sigma per ray — in the
+    order the loop's forward writes, through the trace-position list where that differs — from
+    the host numbers rho and c.  The iteration then launches sphrt_dp_primal_f64 and
+    sphrt_dp_ray_dual_f64 where the scalar one launches sphrt_pd_primal_f64 and
+    sphrt_cp_ray_dual_f64, and sphrt_pd_dual_f64 reads sigma_tv = rho / 2 from a device scalar:
+    the same count of launches, 8 bytes more per voxel and per ray."""
     from . import _lib
     from .raytracer import MatrixFreeOperator
     lib = _lib.load()
@@ -1723,12 +1808,17 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
             cax = [tv.lam * w / n_vox for w in tv.weights]
         else:
             has, ring, cax = [0, 0, 0], 0, [0.0, 0.0, 0.0]
-        # |A|^2 on the operator's own launches: `_normal_direct` of a SquareLoss whose factor
-        # 2 lam / M is 1 applies v -> A^T(A v)
-        ata, pn = _normal_direct(f, y, SquareLoss(lam=n_meas / 2), None, x)
-        LA, _ = _fista_step(ata, x, norm, power_iterations)
-        del ata
-        tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+        if diagonal:
+            pn = lib.sphrt_loss_partials(n_vox)
+            LA = t.zeros(1, dtype=f64, device=dev)
+        else:
+            # |A|^2 on the operator's own launches: `_normal_direct` of a SquareLoss whose factor
+            # 2 lam / M is 1 applies v -> A^T(A v)
+            ata, pn = _normal_direct(f, y, SquareLoss(lam=n_meas / 2), None, x)
+            LA, _ = _fista_step(ata, x, norm, power_iterations)
+            del ata
+            tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+            sigma_tv = sigma
         ps = lib.sphrt_loss_partials(n_meas)
         y_ray, order, res_order, loop_desc, positions, keep = yd.reshape(-1), None, None, None, \
             False, None
@@ -1754,15 +1844,37 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
                 return f(d).reshape(-1)
             return out
 
-        def adjoint():
-            """A^T p -> a buffer the next application may overwrite."""
+        def adjoint(v=None):
+            """A^T p (or A^T v, v in the adjoint's order) -> a buffer the next application may
+            overwrite."""
             if not fused:
-                return f._apply_adjoint((p if p_adj is None else p_adj).view(yd.shape), dshape,
-                                        f64, dev, trace_order=order is not None)
+                if v is None:
+                    v = p if p_adj is None else p_adj
+                return f._apply_adjoint(v.view(yd.shape), dshape, f64, dev,
+                                        trace_order=order is not None)
+            v = p if v is None else v
             if fixed is None:
-                return f._apply_adjoint(p.view(yd.shape), dshape, f64, dev)
-            f._backproject_fixed_into(p, g_buf, fixed)
+                return f._apply_adjoint(v.view(yd.shape), dshape, f64, dev)
+            f._backproject_fixed_into(v, g_buf, fixed)
             return g_buf
+
+        if diagonal:
+            # (ones are ones in every ray order; row in geometry order, sigma where the loop's
+            # forward writes)
+            rho = dual_ratio * s_bar
+            row = f(t.ones_like(x)).reshape(-1)
+            col = adjoint(t.ones(n_meas, dtype=f64, device=dev))
+            tau, sigma = t.empty_like(x), t.empty(n_meas, dtype=f64, device=dev)
+            _lib.check(lib.sphrt_dp_steps_f64(
+                _lib.ptr(col), _lib.ptr(row), n_meas, nr, ne, na, ring, *has, rho, c,
+                _lib.ptr(order if positions else None), _lib.ptr(tau), _lib.ptr(sigma),
+                _lib.stream_of(dev)), 'sphrt_dp_steps_f64')
+            del row, col
+            sigma_tv = t.full((1,), rho / 2, dtype=f64, device=dev)
+        primal, ray_dual = (lib.sphrt_dp_primal_f64, lib.sphrt_dp_ray_dual_f64) if diagonal \
+            else (lib.sphrt_pd_primal_f64, lib.sphrt_cp_ray_dual_f64)
+        primal_name, ray_dual_name = ('sphrt_dp_primal_f64', 'sphrt_dp_ray_dual_f64') if diagonal \
+            else ('sphrt_pd_primal_f64', 'sphrt_cp_ray_dual_f64')
 
         lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
         x = t.where(x < lo, lo, t.where(x > hi, hi, x))
@@ -1787,24 +1899,24 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
                 stream = _lib.stream_of(dev)
                 if stage == 0:
                     g = adjoint()
-                    _lib.check(lib.sphrt_pd_primal_f64(
+                    _lib.check(primal(
                         _lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), nr, ne, na, ring,
                         *has, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
-                        'sphrt_pd_primal_f64')
+                        primal_name)
                 elif stage == 1:
                     if tv is not None:
                         _lib.check(lib.sphrt_pd_dual_f64(
                             _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring, *has,
-                            *cax, _lib.ptr(sigma), _lib.ptr(part_qq[it]), stream),
+                            *cax, _lib.ptr(sigma_tv), _lib.ptr(part_qq[it]), stream),
                             'sphrt_pd_dual_f64')
                 elif stage == 2:
                     zn = forward(x_new, z_new)
                 else:
-                    _lib.check(lib.sphrt_cp_ray_dual_f64(
+                    _lib.check(ray_dual(
                         _lib.ptr(zn), _lib.ptr(z), _lib.ptr(y_ray), y_f64, n_meas, kind, par,
                         _lib.ptr(s_ray), _lib.ptr(w_ray), _lib.ptr(sigma), _lib.ptr(res_order),
                         _lib.ptr(p), _lib.ptr(p_adj), _lib.ptr(part_pp[it]),
-                        _lib.ptr(part_fid[it]), stream), 'sphrt_cp_ray_dual_f64')
+                        _lib.ptr(part_fid[it]), stream), ray_dual_name)
                 stage += 1
 
         try:
@@ -1825,9 +1937,16 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
                           _kernel_sum(t.cat([part_pp[:done], part_fid[:done]]))])
         else:
             sums = LA.new_zeros(0)
-        host = t.cat([sums, LA, tau, sigma]).cpu().tolist()
+        host = t.cat([sums, LA] + ([] if diagonal else [tau, sigma])).cpu().tolist()
         if positions:      # (trace positions back to geometry rays)
             p = t.empty_like(p).index_copy_(0, f._ray_id_long(), p)
+            if diagonal:
+                sigma = t.empty_like(sigma).index_copy_(0, f._ray_id_long(), sigma)
         fids = [s_bar * v for v in host[3 * done:4 * done]]
+        if diagonal:
+            return x, y_hat, _dp_info(
+                _cp_info(host[:done], host[done:2 * done], host[2 * done:3 * done], fids, None,
+                         None, None, q if tv is not None else None, p.view(yd.shape)),
+                tau, sigma.view(yd.shape), rho / 2)
     return x, y_hat, _cp_info(host[:done], host[done:2 * done], host[2 * done:3 * done], fids,
                               *host[-3:], q if tv is not None else None, p.view(yd.shape))
