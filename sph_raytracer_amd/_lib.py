@@ -220,6 +220,15 @@ _DP_SIGNATURES = [
                                    c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp]),
 ]
 DP_EXPORTED = [s[0] for s in _DP_SIGNATURES]
+# and for include/sphrt_iso.h (isotropic TV in primal_dual and chambolle_pock: the primal step
+# with weighted differences and the dual step that projects each voxel's triple onto a ball)
+_ISO_SIGNATURES = [
+    ('sphrt_iso_primal_f64', c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_dbl,
+                                     c_dbl, c_dbl, c_dbl, c_vp, c_dbl, c_dbl, c_vp, c_vp]),
+    ('sphrt_iso_dual_f64', c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_dbl, c_dbl,
+                                   c_dbl, c_dbl, c_vp, c_vp, c_vp]),
+]
+ISO_EXPORTED = [s[0] for s in _ISO_SIGNATURES]
 # sphrt_exact_sort_lists methods and info fields (sphrt.h)
 SORT_SERIAL_AOS, SORT_SERIAL_SOA, SORT_WAVE1, SORT_WAVE4, SORT_NETWORK = range(5)
 SORT_INFO_FIELDS = 4
@@ -245,7 +254,8 @@ def load():
     lib.sphrt_version.argtypes = []
     if not os.environ.get('SPHRT_LIB'):   # an A/B variant may come from other sources
         _check_hash(lib.sphrt_version().decode(), LIB_PATH)
-    for name, res, args in _SIGNATURES + _PD_SIGNATURES + _CP_SIGNATURES + _DP_SIGNATURES:
+    for name, res, args in _SIGNATURES + _PD_SIGNATURES + _CP_SIGNATURES + _DP_SIGNATURES + \
+            _ISO_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:

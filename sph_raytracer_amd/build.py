@@ -44,7 +44,7 @@ def _hash(files, flags):
     h = hashlib.sha256()
     for name, path in [(f, os.path.join(CSRC, f)) for f in sorted(files)] + \
             [(hdr, os.path.join(ROOT, 'include', hdr))
-             for hdr in ('sphrt.h', 'sphrt_pd.h', 'sphrt_cp.h', 'sphrt_dp.h')]:
+             for hdr in ('sphrt.h', 'sphrt_pd.h', 'sphrt_cp.h', 'sphrt_dp.h', 'sphrt_iso.h')]:
         with open(path, 'rb') as fh:
             data = fh.read()
         h.update(name.encode() + b'\0' + str(len(data)).encode() + b'\0' + data)

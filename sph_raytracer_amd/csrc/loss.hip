@@ -26,6 +26,7 @@
 #include "sphrt_pd.h"
 #include "sphrt_cp.h"
 #include "sphrt_dp.h"
+#include "sphrt_iso.h"
 
 namespace sphrt {
 
@@ -550,20 +551,28 @@ struct PdDesc {
 
 // One axis of (D^T q)[i]: + q_ax[lower neighbour] for the edge arriving at i, then - q_ax[i] for
 // the edge leaving it (coordinate c of n along the axis, element stride s).
+// (WEIGHTED — sphrt_iso_primal_f64, include/sphrt_iso.h: the edges carry the axis' weight w, one
+// fma each; with w = 1 the product is exact and the sum is the plain one's, bit for bit)
+template <bool WEIGHTED>
 __device__ __forceinline__ void pd_axis_adjoint(const double* __restrict__ qa, uint32_t i,
                                                 uint32_t c, uint32_t n, uint32_t s, bool wrap,
-                                                double& S) {
+                                                double w, double& S) {
 #pragma clang fp contract(off)
-    if (c > 0 || wrap) S = S + qa[c > 0 ? i - s : i + (n - 1) * s];
-    if (c + 1 < n || wrap) S = S - qa[i];
+    if (c > 0 || wrap) {
+        const double ql = qa[c > 0 ? i - s : i + (n - 1) * s];
+        S = WEIGHTED ? fma(w, ql, S) : S + ql;
+    }
+    if (c + 1 < n || wrap) S = WEIGHTED ? fma(-w, qa[i], S) : S - qa[i];
 }
 
 // (PER_VOXEL: tau holds n steps, one per voxel — sphrt_dp_primal_f64 — instead of one)
-template <bool PER_VOXEL>
+// (WEIGHTED: the adjoint of the weighted differences, w_ax per axis; otherwise w_* are not read)
+template <bool PER_VOXEL, bool WEIGHTED = false>
 __global__ __launch_bounds__(kLossThreads) void pd_primal_kernel(
     const double* __restrict__ x, const double* __restrict__ g, const double* __restrict__ q,
     double* __restrict__ x_new, uint32_t n, PdDesc p, double c_damp,
-    const double* __restrict__ tau, double lower, double upper, double* __restrict__ part_mm) {
+    const double* __restrict__ tau, double lower, double upper, double* __restrict__ part_mm,
+    double w_r = 1.0, double w_e = 1.0, double w_a = 1.0) {
 #pragma clang fp contract(off)
     const double neg_tau0 = PER_VOXEL ? 0.0 : -*tau;
     const uint32_t se = p.na, sr = p.ne * p.na;
@@ -575,9 +584,10 @@ __global__ __launch_bounds__(kLossThreads) void pd_primal_kernel(
         const double xi = x[i];
         const double gp = fma(c_damp, xi, g[i]);
         double S = 0.0;
-        if (p.has_r) pd_axis_adjoint(q, i, r, p.nr, sr, false, S);
-        if (p.has_e) pd_axis_adjoint(q + n, i, e, p.ne, se, false, S);
-        if (p.has_a) pd_axis_adjoint(q + 2 * (size_t)n, i, a, p.na, 1u, p.wrap != 0, S);
+        if (p.has_r) pd_axis_adjoint<WEIGHTED>(q, i, r, p.nr, sr, false, w_r, S);
+        if (p.has_e) pd_axis_adjoint<WEIGHTED>(q + n, i, e, p.ne, se, false, w_e, S);
+        if (p.has_a)
+            pd_axis_adjoint<WEIGHTED>(q + 2 * (size_t)n, i, a, p.na, 1u, p.wrap != 0, w_a, S);
         const double neg_tau = PER_VOXEL ? -tau[i] : neg_tau0;
         const double u = fma(neg_tau, gp + S, xi);
         const double xn = u < lower ? lower : (u > upper ? upper : u);
@@ -628,6 +638,80 @@ __global__ __launch_bounds__(kLossThreads) void pd_dual_kernel(
         if (p.has_a)
             pd_axis_dual(x_new, x_old, q + 2 * (size_t)n, i, xb, a, p.na, 1u, p.wrap != 0, sg,
                          c_a, t);
+        qq += t;
+    }
+    block_partial(qq, part_qq);
+}
+
+// Isotropic TV (include/sphrt_iso.h): one axis of v = q + sigma Dw(2 x_new - x_old) at voxel i,
+// for the edge leaving i, if any -> whether there is one; qo its old dual, v the stepped one.
+__device__ __forceinline__ bool iso_axis_step(const double* __restrict__ x_new,
+                                              const double* __restrict__ x_old, const double* qa,
+                                              uint32_t i, double xb_i, uint32_t c, uint32_t n,
+                                              uint32_t s, bool wrap, double sigma, double w,
+                                              double& qo, double& v) {
+#pragma clang fp contract(off)
+    if (!(c + 1 < n || wrap)) return false;
+    const uint32_t j = c + 1 < n ? i + s : i - (n - 1) * s;
+    const double xb_j = fma(2.0, x_new[j], -x_old[j]);
+    const double e = w * (xb_j - xb_i);
+    qo = qa[i];
+    v = fma(sigma, e, qo);
+    return true;
+}
+
+// The dual step of isotropic TV: the voxel's triple v projected onto the ball of `radius` — one
+// square root and one division per voxel over pd_dual_kernel, the same bytes.  (q in place at the
+// thread's own slots, as in pd_dual_kernel.)
+__global__ __launch_bounds__(kLossThreads) void iso_dual_kernel(
+    const double* __restrict__ x_new, const double* __restrict__ x_old, double* q, uint32_t n,
+    PdDesc p, double w_r, double w_e, double w_a, double radius,
+    const double* __restrict__ sigma, double* __restrict__ part_qq) {
+#pragma clang fp contract(off)
+    const double sg = *sigma;
+    const uint32_t se = p.na, sr = p.ne * p.na;
+    double* const q_r = q;
+    double* const q_e = q + n;
+    double* const q_a = q + 2 * (size_t)n;
+    double qq = 0.0;
+    for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
+         i += gridDim.x * kLossThreads) {
+        const uint32_t q1 = i / p.na, a = i - q1 * p.na;
+        const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+        const double xb = fma(2.0, x_new[i], -x_old[i]);
+        double o_r = 0.0, o_e = 0.0, o_a = 0.0, v_r = 0.0, v_e = 0.0, v_a = 0.0;
+        const bool on_r = p.has_r &&
+            iso_axis_step(x_new, x_old, q_r, i, xb, r, p.nr, sr, false, sg, w_r, o_r, v_r);
+        const bool on_e = p.has_e &&
+            iso_axis_step(x_new, x_old, q_e, i, xb, e, p.ne, se, false, sg, w_e, o_e, v_e);
+        const bool on_a = p.has_a &&
+            iso_axis_step(x_new, x_old, q_a, i, xb, a, p.na, 1u, p.wrap != 0, sg, w_a, o_a, v_a);
+        double n2 = 0.0;
+        if (on_r) n2 = n2 + v_r * v_r;
+        if (on_e) n2 = n2 + v_e * v_e;
+        if (on_a) n2 = n2 + v_a * v_a;
+        const double nrm = sqrt(n2);
+        const bool outside = nrm > radius;              // (a NaN fails the compare: v is stored)
+        const double scale = outside ? radius / nrm : 1.0;
+        double t = 0.0;
+        if (on_r) {
+            const double qn = outside ? v_r * scale : v_r;
+            q_r[i] = qn;
+            const double dq = qn - o_r;
+            t = t + dq * dq;
+        }
+        if (on_e) {
+            const double qn = outside ? v_e * scale : v_e;
+            q_e[i] = qn;
+            const double dq = qn - o_e;
+            t = t + dq * dq;
+        }
+        if (on_a) {
+            const double qn = outside ? v_a * scale : v_a;
+            q_a[i] = qn;
+            const double dq = qn - o_a;
+            t = t + dq * dq;
+        }
         qq += t;
     }
     block_partial(qq, part_qq);
@@ -1103,6 +1187,64 @@ extern "C" int sphrt_pd_dual_f64(const double* x_new, const double* x_old, doubl
                        pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a), c_r, c_e, c_a, sigma,
                        part_qq);
     return check_launch("pd_dual");
+}
+
+// include/sphrt_iso.h: the weights' refusal the two entries share (a NaN fails the compare).
+static int refuse_iso_weights(const char* me, double w_r, double w_e, double w_a) {
+    for (double w : {w_r, w_e, w_a})
+        if (!(w >= 0.0) || __builtin_isinf(w))
+            return fail("%s: the weights w_ax must be finite and >= 0, not %g", me, w);
+    return 0;
+}
+
+extern "C" int sphrt_iso_primal_f64(const double* x, const double* g, const double* q,
+                                    double* x_new, int nr, int ne, int na, int wrap_a, double w_r,
+                                    double w_e, double w_a, double c_damp, const double* tau,
+                                    double lower, double upper, double* part_mm, void* stream) {
+    const char* me = "sphrt_iso_primal_f64";
+    int64_t n = 0;
+    if (int e = refuse_pd(me, nr, ne, na, n)) return e;
+    if (!x || !g || !q || !x_new || !tau || !part_mm) return fail("%s: null buffer", me);
+    if (int e = refuse_iso_weights(me, w_r, w_e, w_a)) return e;
+    if (lower != lower || upper != upper || !(lower < upper))
+        return fail("%s: bounds need lower < upper, neither NaN (%g, %g)", me, lower, upper);
+    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
+    const void* buf[6] = {x, g, x_new, q, part_mm, tau};
+    const int64_t len[6] = {nb, nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
+    for (int a = 0; a < 6; ++a)
+        for (int b = a + 1; b < 6; ++b)
+            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL((pd_primal_kernel<false, true>), dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, x, g, q, x_new, (uint32_t)n,
+                       pd_desc(nr, ne, na, wrap_a, w_r > 0.0, w_e > 0.0, w_a > 0.0), c_damp, tau,
+                       lower, upper, part_mm, w_r, w_e, w_a);
+    return check_launch("iso_primal");
+}
+
+extern "C" int sphrt_iso_dual_f64(const double* x_new, const double* x_old, double* q, int nr,
+                                  int ne, int na, int wrap_a, double w_r, double w_e, double w_a,
+                                  double radius, const double* sigma, double* part_qq,
+                                  void* stream) {
+    const char* me = "sphrt_iso_dual_f64";
+    int64_t n = 0;
+    if (int e = refuse_pd(me, nr, ne, na, n)) return e;
+    if (!x_new || !x_old || !q || !sigma || !part_qq) return fail("%s: null buffer", me);
+    if (int e = refuse_iso_weights(me, w_r, w_e, w_a)) return e;
+    if (!(radius >= 0.0) || __builtin_isinf(radius))
+        return fail("%s: the radius must be finite and >= 0, not %g", me, radius);
+    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
+    const void* buf[5] = {x_new, x_old, q, part_qq, sigma};
+    const int64_t len[5] = {nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
+    for (int a = 0; a < 5; ++a)
+        for (int b = a + 1; b < 5; ++b)
+            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
+    StreamGuard guard(stream);
+    hipLaunchKernelGGL(iso_dual_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, x_new, x_old, q, (uint32_t)n,
+                       pd_desc(nr, ne, na, wrap_a, w_r > 0.0, w_e > 0.0, w_a > 0.0), w_r, w_e,
+                       w_a, radius, sigma, part_qq);
+    return check_launch("iso_dual");
 }
 
 template <typename TY, bool PER_RAY>

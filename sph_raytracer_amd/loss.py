@@ -298,6 +298,64 @@ class _SmoothFunction(t.autograd.Function):
         return ctx.grad * grad_out, None, None
 
 
+class IsoTVRegularizer(Loss):
+    """Isotropic total variation of the density over its trailing axes (r, e, a); every leading
+    axis is batch.  Not in the reference.
+
+        P(d) = (1/N) * sum_i sqrt( sum_ax (w_ax * (D_ax d)[i])^2 )
+
+    with N = d.numel() and D_ax the forward difference of include/sphrt_pd.h: an edge belongs to
+    its lower voxel, (D_ax d)[i] = d[upper neighbour of i] - d[i]; with the azimuth ring closed
+    (``wrap_a``, read as SmoothRegularizer reads it) the wrap edge belongs to the ring's last
+    voxel; an axis of weight 0 or of length 1 has no edges, and a missing edge contributes 0 to
+    its voxel's sum.  With one axis carrying edges P is SmoothRegularizer(kind='abs') of the same
+    weights.
+
+    `compute` is plain torch on every device and differentiable; where all of a voxel's
+    differences vanish the gradient is 0 (the square root is masked before and after), not NaN.
+    `gd` runs the class through autograd; `primal_dual` and `chambolle_pock` take it as their TV
+    term and never differentiate it (include/sphrt_iso.h)."""
+
+    def __init__(self, weights=(1, 1, 1), wrap_a=None, **kwargs):
+        try:
+            weights = tuple(weights)
+        except TypeError:
+            weights = ()
+        if len(weights) != 3 or not all(SmoothRegularizer._weight(w) for w in weights):
+            raise ValueError('IsoTVRegularizer needs three weights (w_r, w_e, w_a), real numbers '
+                             f'that are finite and >= 0, not {weights!r}')
+        if wrap_a is not None and not isinstance(wrap_a, bool):
+            raise ValueError(f'wrap_a must be True, False or None, not {wrap_a!r}')
+        self.weights = tuple(float(w) for w in weights)
+        self.wrap_a = wrap_a
+        super().__init__(**kwargs)
+
+    wraps = SmoothRegularizer.wraps
+
+    def formula(self, d, wrap):
+        """The penalty in plain torch (differentiable): narrow, roll, a masked sqrt."""
+        if d.dim() < 3:
+            raise ValueError(f'IsoTVRegularizer needs a density with axes (..., r, e, a), not '
+                             f'shape {tuple(d.shape)}')
+        n2 = t.zeros_like(d)
+        for dim, w in zip((-3, -2, -1), self.weights):
+            n = d.shape[dim]
+            if not (w > 0 and n > 1):
+                continue
+            if dim == -1 and wrap:
+                n2 = n2 + (w * (t.roll(d, -1, -1) - d)) ** 2
+            else:
+                e = w * (d.narrow(dim, 1, n - 1) - d.narrow(dim, 0, n - 1))
+                pad = [0, 0] * (-dim - 1) + [0, 1]       # (one zero after the axis' last voxel)
+                n2 = n2 + t.nn.functional.pad(e ** 2, pad)
+        live = n2 != 0                   # (a NaN stays live)
+        root = t.sqrt(t.where(live, n2, t.ones_like(n2)))
+        return t.where(live, root, t.zeros_like(root)).sum() / d.numel()
+
+    def compute(self, f, y, d, c):
+        return self.formula(_scaled(self.volume_mask, d), self.wraps(f))
+
+
 class NegSumRegularizer(Loss):
     """Summed magnitude of negative voxels."""
 

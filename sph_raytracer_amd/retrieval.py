@@ -14,8 +14,8 @@ import math
 
 import torch as t
 
-from .loss import (AbsLoss, HuberLoss, NegRegularizer, PoissonLoss, SmoothRegularizer,
-                   SquareLoss)
+from .loss import (AbsLoss, HuberLoss, IsoTVRegularizer, NegRegularizer, PoissonLoss,
+                   SmoothRegularizer, SquareLoss)
 from .model import FullyDenseModel
 
 try:
@@ -1182,41 +1182,63 @@ def primal_dual(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=0.0
     optimality)}.  No tolerance, no early exit; every iterate satisfies the bounds and every
     |q_ax| <= c_ax exactly.
 
+    Isotropic TV: exactly one IsoTVRegularizer may stand in place of the abs term (under the same
+    rules: a scalar lam > 0, unit masks, use_grad, an axis with edges; both, or two of them,
+    raise ValueError).  The term is r sum_i |(Dw x)_i|_2 with Dw_ax = w_ax D_ax and r = lam_tv / V;
+    B = 4 sum of w_ax^2 over the axes with edges >= |Dw|^2, s = Dw^T q, and the dual step is the
+    projection of each voxel's triple onto the ball of radius r:
+
+        v_ax = fma(sigma, (Dw xb)_ax, q_ax);  nrm = sqrt(sum_ax v_ax^2)
+        q_ax <- v_ax (r / nrm) if nrm > r else v_ax                 (include/sphrt_iso.h)
+
+    info keeps its keys; info['dual'] has shape (3,) + x.shape and certifies optimality with
+    |q_i|_2 <= r up to sum_ax q_ax^2 <= r^2 (1 + 12 * 2^-53) (the header derives the bound; scale q
+    by 1 / (1 + 12 * 2^-53) before using it as a feasible point).
+
     The inputs `cg` runs directly (`_cg_is_direct`) run `_primal_dual_direct`: the operator's own
-    launches and two csrc/loss.hip launches per iteration (include/sphrt_pd.h), the whole solve
+    launches and two csrc/loss.hip launches per iteration (include/sphrt_pd.h, or with an
+    IsoTVRegularizer include/sphrt_iso.h's two in their place), the whole solve
     enqueued without a host sync and bitwise reproducible where the adjoint is.  Everything else
     runs the same algorithm in plain torch (`_primal_dual_generic`)."""
     who = 'primal_dual'
     tvs = [fn for fn in loss_fns if type(fn) is SmoothRegularizer and fn.smooth_kind == 'abs']
-    rest = [fn for fn in loss_fns if not any(fn is v for v in tvs)]
+    isos = [fn for fn in loss_fns if type(fn) is IsoTVRegularizer]
+    rest = [fn for fn in loss_fns if not any(fn is v for v in tvs + isos)]
     sq, smooth = _cg_terms(y, rest, damp, 0.0, num_iterations, who=who)
-    if not tvs:
+    if isos and tvs:
+        raise ValueError(f"{who} solves with one TV term: an IsoTVRegularizer beside a "
+                         "SmoothRegularizer(kind='abs') is not built")
+    if len(isos) > 1:
+        raise ValueError(f'{who} solves with one IsoTVRegularizer, not {len(isos)}')
+    if not tvs and not isos:
         raise ValueError(f"{who} needs one SmoothRegularizer(kind='abs') among loss_fns (fista "
                          'solves the total without it)')
     if len(tvs) > 1:
         raise ValueError(f"{who} solves with one SmoothRegularizer(kind='abs'), not {len(tvs)}")
-    tv = tvs[0]
+    tv = (isos or tvs)[0]
+    cls, label = ('IsoTVRegularizer', 'IsoTVRegularizer') if isos else \
+        ('SmoothRegularizer', "SmoothRegularizer(kind='abs')")
     if not tv.use_grad:
-        raise ValueError(f'{who}: SmoothRegularizer(use_grad=False) is a monitor, not a term of '
+        raise ValueError(f'{who}: {cls}(use_grad=False) is a monitor, not a term of '
                          'the total')
     if not _number(tv.lam) or not 0 < tv.lam < math.inf:
-        raise ValueError(f"{who} needs a finite scalar lam > 0 on SmoothRegularizer(kind='abs'), "
+        raise ValueError(f"{who} needs a finite scalar lam > 0 on {label}, "
                          f'not lam = {tv.lam!r}')
     if not _unit(tv.volume_mask):
-        raise ValueError(f"{who} does not take a volume_mask (SmoothRegularizer(kind='abs'))")
+        raise ValueError(f"{who} does not take a volume_mask ({label})")
     if not _unit(tv.projection_mask):
-        raise ValueError(f"{who}: the projection_mask of SmoothRegularizer(kind='abs') must be 1")
+        raise ValueError(f"{who}: the projection_mask of {label} must be 1")
     bounds = _fista_args(lower, upper, lipschitz, power_iterations, who=who)
     if not _number(dual_ratio) or not 0 < dual_ratio < math.inf:
         raise ValueError(f'{who} needs a finite dual_ratio > 0, not {dual_ratio!r}')
     shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
     if len(shape) < 3:
         raise ValueError(f'{who} needs a volume with axes (..., r, e, a), not shape {shape}')
-    if len(shape) > 3 and tv.time_weight > 0:
+    if len(shape) > 3 and not isos and tv.time_weight > 0:
         raise ValueError(f"{who}: SmoothRegularizer(kind='abs', time_weight={tv.time_weight!r}) "
                          'on a volume with a time axis is not built (time_weight=0 is)')
     if not any(_pd_axes(tv, shape)):
-        raise ValueError(f"{who}: SmoothRegularizer(kind='abs', weights={tv.weights!r}) has no "
+        raise ValueError(f"{who}: {_tv_label(tv)} has no "
                          f'edges on a volume of shape {shape} (an axis needs a weight > 0 and a '
                          'length > 1)')
     bar = _Bar(range(num_iterations), progress_bar)
@@ -1231,9 +1253,42 @@ def _pd_axes(tv, shape):
     return [w > 0 and n > 1 for w, n in zip(tv.weights, shape[-3:])]
 
 
+def _is_iso(tv):
+    return type(tv) is IsoTVRegularizer
+
+
+def _tv_label(tv):
+    """The TV term as the refusals name it."""
+    if _is_iso(tv):
+        return f'IsoTVRegularizer(weights={tv.weights!r})'
+    return f"SmoothRegularizer(kind='abs', weights={tv.weights!r})"
+
+
+def _tv_bound(tv, has):
+    """B / 4 of the TV term's difference operator, B >= |D|^2: the number of axes with edges
+    (kind='abs': the weights sit in the clamps, D is unweighted), or for an IsoTVRegularizer the
+    sum of w_ax^2 over them (each 1-D difference operator's bound of 4, scaled by its weight and
+    stacked)."""
+    if _is_iso(tv):
+        return sum(w * w for w, h in zip(tv.weights, has) if h)
+    return sum(has)
+
+
+def _tv_launches(tv, has, n_vox):
+    """(primal entry, TV-dual entry, the primal's axis arguments, the dual's axis arguments) of the
+    direct loops' two volume launches: include/sphrt_pd.h's with the has_* flags and the clamps
+    c_ax = lam w_ax / V, or for an IsoTVRegularizer include/sphrt_iso.h's with the weights and
+    the radius lam / V."""
+    if _is_iso(tv):
+        return ('sphrt_iso_primal_f64', 'sphrt_iso_dual_f64', list(tv.weights),
+                list(tv.weights) + [tv.lam / n_vox])
+    return ('sphrt_pd_primal_f64', 'sphrt_pd_dual_f64', list(has),
+            list(has) + [tv.lam * w / n_vox for w in tv.weights])
+
+
 def _pd_steps(L, dual_ratio, n_axes):
     """(tau, sigma) as one-element tensors beside L: 1 / ((1 + ratio) L) and ratio L / B with
-    B = 4 n_axes; both 0 when L is not > 0 (`_fista_step`'s rule for its step)."""
+    B = 4 n_axes (`_tv_bound`); both 0 when L is not > 0 (`_fista_step`'s rule for its step)."""
     zero = t.zeros_like(L)
     tau = t.where(L > 0, 1.0 / ((1.0 + dual_ratio) * L), zero)
     sigma = t.where(L > 0, (dual_ratio * L) / (4.0 * n_axes), zero)
@@ -1297,6 +1352,62 @@ def _tv_generic(tv, f, x):
     return has, adjoint, dual
 
 
+def _iso_generic(tv, f, x):
+    """`_tv_generic` for an IsoTVRegularizer, over the r, e, a axes of every slice of volumes like
+    `x`: the specification of include/sphrt_iso.h's two launches and the CPU path -> (has,
+    adjoint, dual) with adjoint(q) = Dw^T q, Dw_ax = w_ax D_ax, and dual(q, xb, sigma) = each
+    voxel's triple q + sigma Dw xb projected onto the ball of radius lam / V (v itself where its
+    norm is not greater; a slot without an edge holds +0.0 and adds nothing to the norm)."""
+    has, ring = _pd_axes(tv, x.shape), tv.wraps(f) and x.shape[-1] > 1
+    radius = t.full((), tv.lam / x.numel(), dtype=x.dtype, device=x.device)
+    wts = tv.weights
+
+    def edges(v, ax):
+        if ax == 2 and ring:
+            return None
+        n = v.shape[ax - 3]
+        return v.narrow(ax - 3, 0, n - 1), v.narrow(ax - 3, 1, n - 1)
+
+    def adjoint(q):
+        s = t.zeros_like(q[0])     # Dw^T q: the arriving edge, then the leaving one
+        for ax in range(3):
+            if not has[ax]:
+                continue
+            if edges(s, ax) is None:
+                s.add_(t.roll(q[ax], 1, -1), alpha=wts[ax])
+                s.sub_(q[ax], alpha=wts[ax])
+            else:
+                edges(s, ax)[1].add_(edges(q[ax], ax)[0], alpha=wts[ax])
+                edges(s, ax)[0].sub_(edges(q[ax], ax)[0], alpha=wts[ax])
+        return s
+
+    def dual(q, xb, sigma):
+        v = q.clone()
+        for ax in range(3):
+            if not has[ax]:
+                continue
+            if edges(xb, ax) is None:
+                v[ax] = t.addcmul(q[ax], wts[ax] * (t.roll(xb, -1, -1) - xb), sigma)
+            else:
+                below, above = edges(xb, ax)
+                edges(v[ax], ax)[0].copy_(
+                    t.addcmul(edges(q[ax], ax)[0], wts[ax] * (above - below), sigma))
+        n2 = t.zeros_like(v[0])
+        for ax in range(3):
+            if has[ax]:
+                n2 = n2 + v[ax] * v[ax]
+        nrm = t.sqrt(n2)
+        outside = nrm > radius
+        scale = radius / t.where(outside, nrm, t.ones_like(nrm))
+        return t.where(outside, v * scale, v)
+    return has, adjoint, dual
+
+
+def _tv_maps(tv, f, x):
+    """(has, adjoint, dual) of the TV term of either class."""
+    return _iso_generic(tv, f, x) if _is_iso(tv) else _tv_generic(tv, f, x)
+
+
 def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, upper, lipschitz,
                          power_iterations, dual_ratio, bar):
     """`primal_dual` in plain torch, through f(x) and f._apply_adjoint alone: the specification
@@ -1309,7 +1420,7 @@ def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, 
         n_vox = x.numel()
         c = 2 * damp / n_vox
         normal = _normal_generic(f, yd, sq, smooth, x)
-        has, tv_adjoint, tv_dual = _tv_generic(tv, f, x)
+        has, tv_adjoint, tv_dual = _tv_maps(tv, f, x)
         lo, hi = (t.full((), v, dtype=x.dtype, device=x.device) for v in (lower, upper))
 
         def clamp(u, a, b):
@@ -1317,7 +1428,7 @@ def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, 
 
         L, _ = _fista_step(lambda v: t.add(normal(v, None), v, alpha=c), x, lipschitz,
                            power_iterations)
-        tau, sigma = _pd_steps(L, dual_ratio, sum(has))
+        tau, sigma = _pd_steps(L, dual_ratio, _tv_bound(tv, has))
         x = clamp(x, lo, hi)
         q = x.new_zeros((3,) + tuple(x.shape))
         mms, qqs = [], []
@@ -1362,10 +1473,11 @@ def _primal_dual_direct(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, u
         c = 2 * damp / n_vox
         has = [int(h) for h in _pd_axes(tv, x.shape)]
         ring = int(tv.wraps(f) and na > 1)
-        cax = [tv.lam * w / n_vox for w in tv.weights]
+        primal_name, dual_name, p_args, d_args = _tv_launches(tv, has, n_vox)
+        primal, dual = getattr(lib, primal_name), getattr(lib, dual_name)
         apply, pn = _normal_direct(f, y, sq, smooth, x)
         L, _ = _fista_step(lambda v: t.add(apply(v), v, alpha=c), x, lipschitz, power_iterations)
-        tau, sigma = _pd_steps(L, dual_ratio, sum(has))
+        tau, sigma = _pd_steps(L, dual_ratio, _tv_bound(tv, has))
         lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
         x = t.where(x < lo, lo, t.where(x > hi, hi, x))
         x_new = t.empty_like(x)
@@ -1380,13 +1492,13 @@ def _primal_dual_direct(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, u
             for it in bar:
                 g = apply(x, True)
                 stream = _lib.stream_of(dev)
-                _lib.check(lib.sphrt_pd_primal_f64(
+                _lib.check(primal(
                     _lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), nr, ne, na, ring,
-                    *has, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
-                    'sphrt_pd_primal_f64')
-                _lib.check(lib.sphrt_pd_dual_f64(
-                    _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring, *has, *cax,
-                    _lib.ptr(sigma), _lib.ptr(part_qq[it]), stream), 'sphrt_pd_dual_f64')
+                    *p_args, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
+                    primal_name)
+                _lib.check(dual(
+                    _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring, *d_args,
+                    _lib.ptr(sigma), _lib.ptr(part_qq[it]), stream), dual_name)
                 dual_out = it
                 x, x_new, done = x_new, x, it + 1      # (one statement: not separable)
         except KeyboardInterrupt:
@@ -1486,6 +1598,14 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
     info['norm'] None; the histories keep their meaning.  Whether it pays depends on the problem:
     README and DESIGN section 8 record the measurement.
 
+    Isotropic TV: one IsoTVRegularizer may stand in place of the abs term, under `primal_dual`'s
+    rules for it and with its dual step (the projection of each voxel's triple onto the ball of
+    radius lam_tv / V; sphrt_iso_primal_f64 and sphrt_iso_dual_f64 in place of the two launches
+    of sphrt_pd.h); B = 4 sum of w_ax^2 over the axes with edges in Kn^2.  info['dual'] then has
+    shape (3,) + x.shape and certifies with |q_i|_2 <= r up to sum_ax q_ax^2 <= r^2 (1 + 12 *
+    2^-53).  precondition='diagonal' with it raises ValueError: the lemma's per-row steps do not
+    fit a prox that couples three rows.
+
     The inputs `cg` runs directly (`_cg_is_direct`) run `_chambolle_pock_direct`: the operator's
     own launches and three csrc/loss.hip launches per iteration (two without TV), the whole solve
     enqueued without a host sync and bitwise reproducible where the adjoint is.  Over a
@@ -1506,16 +1626,20 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
     if precondition is not None and norm is not None:
         raise ValueError(f"{who}: precondition='diagonal' takes its steps from the operator's row "
                          f'and column sums, not from a norm (norm={norm!r})')
+    if precondition is not None and _is_iso(tv):
+        raise ValueError(f"{who}: precondition='diagonal' with an IsoTVRegularizer is not built "
+                         '(per-row steps do not fit a prox that couples three rows; '
+                         "SmoothRegularizer(kind='abs') and precondition=None are)")
     if tv is not None:
         shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
         if len(shape) < 3:
             raise ValueError(f'{who} needs a volume with axes (..., r, e, a), not shape {shape}')
-        if len(shape) > 3 and tv.time_weight > 0:
+        if len(shape) > 3 and not _is_iso(tv) and tv.time_weight > 0:
             raise ValueError(f"{who}: SmoothRegularizer(kind='abs', time_weight="
                              f'{tv.time_weight!r}) on a volume with a time axis is not built '
                              '(time_weight=0 is)')
         if not any(_pd_axes(tv, shape)):
-            raise ValueError(f"{who}: SmoothRegularizer(kind='abs', weights={tv.weights!r}) has "
+            raise ValueError(f"{who}: {_tv_label(tv)} has "
                              f'no edges on a volume of shape {shape} (an axis needs a weight > 0 '
                              'and a length > 1)')
     bar = _Bar(range(num_iterations), progress_bar)
@@ -1547,9 +1671,19 @@ def _cp_terms(y, loss_fns, damp, num_iterations, who):
                 raise ValueError(f"{who} takes a smooth term as total variation only: "
                                  f"SmoothRegularizer(kind={fn.smooth_kind!r}) is not built "
                                  "(kind='abs' is)")
+            if _is_iso(tv):
+                raise ValueError(f"{who} solves with at most one TV term: a SmoothRegularizer("
+                                 "kind='abs') beside an IsoTVRegularizer is not built")
             if tv is not None:
                 raise ValueError(f"{who} solves with at most one SmoothRegularizer(kind='abs'), "
                                  'not two')
+            tv = fn
+        elif _is_iso(fn):
+            if _is_iso(tv):
+                raise ValueError(f'{who} solves with at most one IsoTVRegularizer, not two')
+            if tv is not None:
+                raise ValueError(f"{who} solves with at most one TV term: an IsoTVRegularizer "
+                                 "beside a SmoothRegularizer(kind='abs') is not built")
             tv = fn
         else:
             raise ValueError(f'{who} needs a total of one SquareLoss, AbsLoss, HuberLoss or '
@@ -1691,7 +1825,7 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
             fid.projection_mask.detach().to(pdt).expand(yd.shape)
         s = t.full_like(m, s_bar) if w is None else s_bar * w
         lo, hi = (t.full((), v, dtype=dtype, device=dev) for v in (lower, upper))
-        has, tv_adjoint, tv_dual = _tv_generic(tv, f, x) if tv is not None else ([], None, None)
+        has, tv_adjoint, tv_dual = _tv_maps(tv, f, x) if tv is not None else ([], None, None)
         if diagonal:
             # row and column sums of A >= 0: one forward and one adjoint of ones
             rho_s = dual_ratio * s_bar
@@ -1705,7 +1839,7 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
             # |A|^2: v -> A^T(A v) is `_normal_generic` of a SquareLoss whose factor 2 lam / M is 1
             ata = _normal_generic(f, yd, SquareLoss(lam=n_meas / 2), None, x)
             LA, _ = _fista_step(lambda v: ata(v, None), x, norm, power_iterations)
-            tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+            tau, sigma = _cp_steps(LA, _tv_bound(tv, has), s_bar, c, dual_ratio)
             sigma_tv = sigma
         x = t.where(x < lo, lo, t.where(x > hi, hi, x))
         q = x.new_zeros((3,) + dshape) if tv is not None else None
@@ -1817,7 +1951,7 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
             ata, pn = _normal_direct(f, y, SquareLoss(lam=n_meas / 2), None, x)
             LA, _ = _fista_step(ata, x, norm, power_iterations)
             del ata
-            tau, sigma = _cp_steps(LA, sum(has), s_bar, c, dual_ratio)
+            tau, sigma = _cp_steps(LA, _tv_bound(tv, has), s_bar, c, dual_ratio)
             sigma_tv = sigma
         ps = lib.sphrt_loss_partials(n_meas)
         y_ray, order, res_order, loop_desc, positions, keep = yd.reshape(-1), None, None, None, \
@@ -1875,6 +2009,11 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
             else (lib.sphrt_pd_primal_f64, lib.sphrt_cp_ray_dual_f64)
         primal_name, ray_dual_name = ('sphrt_dp_primal_f64', 'sphrt_dp_ray_dual_f64') if diagonal \
             else ('sphrt_pd_primal_f64', 'sphrt_cp_ray_dual_f64')
+        p_args, d_args, tv_dual, tv_dual_name = has, has + cax, lib.sphrt_pd_dual_f64, \
+            'sphrt_pd_dual_f64'
+        if _is_iso(tv):        # (never with `diagonal`: refused by chambolle_pock)
+            primal_name, tv_dual_name, p_args, d_args = _tv_launches(tv, has, n_vox)
+            primal, tv_dual = getattr(lib, primal_name), getattr(lib, tv_dual_name)
 
         lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
         x = t.where(x < lo, lo, t.where(x > hi, hi, x))
@@ -1901,14 +2040,14 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
                     g = adjoint()
                     _lib.check(primal(
                         _lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), nr, ne, na, ring,
-                        *has, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
+                        *p_args, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
                         primal_name)
                 elif stage == 1:
                     if tv is not None:
-                        _lib.check(lib.sphrt_pd_dual_f64(
-                            _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring, *has,
-                            *cax, _lib.ptr(sigma_tv), _lib.ptr(part_qq[it]), stream),
-                            'sphrt_pd_dual_f64')
+                        _lib.check(tv_dual(
+                            _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring,
+                            *d_args, _lib.ptr(sigma_tv), _lib.ptr(part_qq[it]), stream),
+                            tv_dual_name)
                 elif stage == 2:
                     zn = forward(x_new, z_new)
                 else:
