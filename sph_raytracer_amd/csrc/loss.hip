@@ -549,6 +549,16 @@ struct PdDesc {
     int wrap;                   // the azimuth ring is closed (and na > 1)
 };
 
+// Voxel i as (r, e, a), with the element strides sr and se of the r and e axes (a's is 1).
+struct PdVoxel {
+    uint32_t r, e, a, sr, se;
+};
+__device__ __forceinline__ PdVoxel pd_voxel(const PdDesc& p, uint32_t i) {
+    const uint32_t q1 = i / p.na, a = i - q1 * p.na;
+    const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+    return PdVoxel{r, e, a, p.ne * p.na, p.na};
+}
+
 // One axis of (D^T q)[i]: + q_ax[lower neighbour] for the edge arriving at i, then - q_ax[i] for
 // the edge leaving it (coordinate c of n along the axis, element stride s).
 // (WEIGHTED — sphrt_iso_primal_f64, include/sphrt_iso.h: the edges carry the axis' weight w, one
@@ -575,19 +585,17 @@ __global__ __launch_bounds__(kLossThreads) void pd_primal_kernel(
     double w_r = 1.0, double w_e = 1.0, double w_a = 1.0) {
 #pragma clang fp contract(off)
     const double neg_tau0 = PER_VOXEL ? 0.0 : -*tau;
-    const uint32_t se = p.na, sr = p.ne * p.na;
     double mm = 0.0;
     for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
          i += gridDim.x * kLossThreads) {
-        const uint32_t q1 = i / p.na, a = i - q1 * p.na;
-        const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+        const PdVoxel v = pd_voxel(p, i);
         const double xi = x[i];
         const double gp = fma(c_damp, xi, g[i]);
         double S = 0.0;
-        if (p.has_r) pd_axis_adjoint<WEIGHTED>(q, i, r, p.nr, sr, false, w_r, S);
-        if (p.has_e) pd_axis_adjoint<WEIGHTED>(q + n, i, e, p.ne, se, false, w_e, S);
+        if (p.has_r) pd_axis_adjoint<WEIGHTED>(q, i, v.r, p.nr, v.sr, false, w_r, S);
+        if (p.has_e) pd_axis_adjoint<WEIGHTED>(q + n, i, v.e, p.ne, v.se, false, w_e, S);
         if (p.has_a)
-            pd_axis_adjoint<WEIGHTED>(q + 2 * (size_t)n, i, a, p.na, 1u, p.wrap != 0, w_a, S);
+            pd_axis_adjoint<WEIGHTED>(q + 2 * (size_t)n, i, v.a, p.na, 1u, p.wrap != 0, w_a, S);
         const double neg_tau = PER_VOXEL ? -tau[i] : neg_tau0;
         const double u = fma(neg_tau, gp + S, xi);
         const double xn = u < lower ? lower : (u > upper ? upper : u);
@@ -598,19 +606,36 @@ __global__ __launch_bounds__(kLossThreads) void pd_primal_kernel(
     block_partial(mm, part_mm);
 }
 
-// One axis of the dual update at voxel i (xb_i = 2 x_new[i] - x_old[i]): the edge leaving i, if
-// any, takes v = fma(sigma, xb_j - xb_i, q) clamped to +-c, and its squared change goes onto t.
+// One axis of v = q + sigma Dw xb at voxel i (xb = 2 x_new - x_old, xb_i that of i), for the edge
+// leaving i, if any (coordinate c of n along the axis, element stride s; its upper voxel j) ->
+// whether there is one; qo its old dual, v = fma(sigma, w (xb_j - xb_i), qo) the stepped one.
+// (WEIGHTED — include/sphrt_iso.h: the multiply by the axis' weight w; otherwise w is not read)
+template <bool WEIGHTED>
+__device__ __forceinline__ bool pd_edge_step(const double* __restrict__ x_new,
+                                             const double* __restrict__ x_old, const double* qa,
+                                             uint32_t i, double xb_i, uint32_t c, uint32_t n,
+                                             uint32_t s, bool wrap, double sigma, double w,
+                                             double& qo, double& v) {
+#pragma clang fp contract(off)
+    if (!(c + 1 < n || wrap)) return false;
+    const uint32_t j = c + 1 < n ? i + s : i - (n - 1) * s;
+    const double xb_j = fma(2.0, x_new[j], -x_old[j]);
+    qo = qa[i];
+    const double d = WEIGHTED ? w * (xb_j - xb_i) : xb_j - xb_i;
+    v = fma(sigma, d, qo);
+    return true;
+}
+
+// One axis of the dual update at voxel i: the edge leaving i, if any, takes the stepped v clamped
+// to +-c, and its squared change goes onto t.
 __device__ __forceinline__ void pd_axis_dual(const double* __restrict__ x_new,
                                              const double* __restrict__ x_old, double* qa,
                                              uint32_t i, double xb_i, uint32_t c, uint32_t n,
                                              uint32_t s, bool wrap, double sigma, double cax,
                                              double& t) {
 #pragma clang fp contract(off)
-    if (!(c + 1 < n || wrap)) return;
-    const uint32_t j = c + 1 < n ? i + s : i - (n - 1) * s;
-    const double xb_j = fma(2.0, x_new[j], -x_old[j]);
-    const double qo = qa[i];
-    const double v = fma(sigma, xb_j - xb_i, qo);
+    double qo, v;
+    if (!pd_edge_step<false>(x_new, x_old, qa, i, xb_i, c, n, s, wrap, sigma, 1.0, qo, v)) return;
     const double qn = v < -cax ? -cax : (v > cax ? cax : v);
     qa[i] = qn;
     const double dq = qn - qo;
@@ -625,42 +650,24 @@ __global__ __launch_bounds__(kLossThreads) void pd_dual_kernel(
     double* __restrict__ part_qq) {
 #pragma clang fp contract(off)
     const double sg = *sigma;
-    const uint32_t se = p.na, sr = p.ne * p.na;
     double qq = 0.0;
     for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
          i += gridDim.x * kLossThreads) {
-        const uint32_t q1 = i / p.na, a = i - q1 * p.na;
-        const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+        const PdVoxel v = pd_voxel(p, i);
         const double xb = fma(2.0, x_new[i], -x_old[i]);
         double t = 0.0;
-        if (p.has_r) pd_axis_dual(x_new, x_old, q, i, xb, r, p.nr, sr, false, sg, c_r, t);
-        if (p.has_e) pd_axis_dual(x_new, x_old, q + n, i, xb, e, p.ne, se, false, sg, c_e, t);
+        if (p.has_r) pd_axis_dual(x_new, x_old, q, i, xb, v.r, p.nr, v.sr, false, sg, c_r, t);
+        if (p.has_e) pd_axis_dual(x_new, x_old, q + n, i, xb, v.e, p.ne, v.se, false, sg, c_e, t);
         if (p.has_a)
-            pd_axis_dual(x_new, x_old, q + 2 * (size_t)n, i, xb, a, p.na, 1u, p.wrap != 0, sg,
+            pd_axis_dual(x_new, x_old, q + 2 * (size_t)n, i, xb, v.a, p.na, 1u, p.wrap != 0, sg,
                          c_a, t);
         qq += t;
     }
     block_partial(qq, part_qq);
 }
 
-// Isotropic TV (include/sphrt_iso.h): one axis of v = q + sigma Dw(2 x_new - x_old) at voxel i,
-// for the edge leaving i, if any -> whether there is one; qo its old dual, v the stepped one.
-__device__ __forceinline__ bool iso_axis_step(const double* __restrict__ x_new,
-                                              const double* __restrict__ x_old, const double* qa,
-                                              uint32_t i, double xb_i, uint32_t c, uint32_t n,
-                                              uint32_t s, bool wrap, double sigma, double w,
-                                              double& qo, double& v) {
-#pragma clang fp contract(off)
-    if (!(c + 1 < n || wrap)) return false;
-    const uint32_t j = c + 1 < n ? i + s : i - (n - 1) * s;
-    const double xb_j = fma(2.0, x_new[j], -x_old[j]);
-    const double e = w * (xb_j - xb_i);
-    qo = qa[i];
-    v = fma(sigma, e, qo);
-    return true;
-}
-
-// The dual step of isotropic TV: the voxel's triple v projected onto the ball of `radius` — one
+// The dual step of isotropic TV (include/sphrt_iso.h): the voxel's triple v of weighted edge
+// steps projected onto the ball of `radius` — one
 // square root and one division per voxel over pd_dual_kernel, the same bytes.  (q in place at the
 // thread's own slots, as in pd_dual_kernel.)
 __global__ __launch_bounds__(kLossThreads) void iso_dual_kernel(
@@ -669,23 +676,21 @@ __global__ __launch_bounds__(kLossThreads) void iso_dual_kernel(
     const double* __restrict__ sigma, double* __restrict__ part_qq) {
 #pragma clang fp contract(off)
     const double sg = *sigma;
-    const uint32_t se = p.na, sr = p.ne * p.na;
     double* const q_r = q;
     double* const q_e = q + n;
     double* const q_a = q + 2 * (size_t)n;
     double qq = 0.0;
     for (uint32_t i = blockIdx.x * kLossThreads + threadIdx.x; i < n;
          i += gridDim.x * kLossThreads) {
-        const uint32_t q1 = i / p.na, a = i - q1 * p.na;
-        const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+        const PdVoxel c = pd_voxel(p, i);
         const double xb = fma(2.0, x_new[i], -x_old[i]);
         double o_r = 0.0, o_e = 0.0, o_a = 0.0, v_r = 0.0, v_e = 0.0, v_a = 0.0;
-        const bool on_r = p.has_r &&
-            iso_axis_step(x_new, x_old, q_r, i, xb, r, p.nr, sr, false, sg, w_r, o_r, v_r);
-        const bool on_e = p.has_e &&
-            iso_axis_step(x_new, x_old, q_e, i, xb, e, p.ne, se, false, sg, w_e, o_e, v_e);
-        const bool on_a = p.has_a &&
-            iso_axis_step(x_new, x_old, q_a, i, xb, a, p.na, 1u, p.wrap != 0, sg, w_a, o_a, v_a);
+        const bool on_r = p.has_r && pd_edge_step<true>(x_new, x_old, q_r, i, xb, c.r, p.nr, c.sr,
+                                                        false, sg, w_r, o_r, v_r);
+        const bool on_e = p.has_e && pd_edge_step<true>(x_new, x_old, q_e, i, xb, c.e, p.ne, c.se,
+                                                        false, sg, w_e, o_e, v_e);
+        const bool on_a = p.has_a && pd_edge_step<true>(x_new, x_old, q_a, i, xb, c.a, p.na, 1u,
+                                                        p.wrap != 0, sg, w_a, o_a, v_a);
         double n2 = 0.0;
         if (on_r) n2 = n2 + v_r * v_r;
         if (on_e) n2 = n2 + v_e * v_e;
@@ -786,12 +791,11 @@ __global__ __launch_bounds__(kLossThreads) void dp_steps_kernel(
     for (uint32_t j = blockIdx.x * kLossThreads + threadIdx.x; j < n;
          j += gridDim.x * kLossThreads) {
         if (j < n_vox) {
-            const uint32_t q1 = j / p.na, a = j - q1 * p.na;
-            const uint32_t r = q1 / p.ne, e = q1 - r * p.ne;
+            const PdVoxel v = pd_voxel(p, j);
             int deg = 0;
-            if (p.has_r) deg += (r > 0) + (r + 1 < p.nr);
-            if (p.has_e) deg += (e > 0) + (e + 1 < p.ne);
-            if (p.has_a) deg += p.wrap ? 2 : (a > 0) + (a + 1 < p.na);
+            if (p.has_r) deg += (v.r > 0) + (v.r + 1 < p.nr);
+            if (p.has_e) deg += (v.e > 0) + (v.e + 1 < p.ne);
+            if (p.has_a) deg += p.wrap ? 2 : (v.a > 0) + (v.a + 1 < p.na);
             const double d = fma(rho, col[j] + (double)deg, c);
             tau[j] = d > 0.0 ? 1.0 / d : 0.0;
         }
@@ -811,6 +815,18 @@ static unsigned loss_grid(int64_t n) {
 static bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb ? pb - pa < (uintptr_t)na : pa - pb < (uintptr_t)nb;
+}
+
+// The alias refusal of the pd, iso, dp and cp entries: each of the first n_outputs of the n
+// buffers against every buffer after it (all of them: n_outputs = n); a null one — an optional
+// buffer left out — is skipped.
+static int refuse_aliased(const char* me, const void* const* buf, const int64_t* len,
+                          int n_outputs, int n) {
+    for (int a = 0; a < n_outputs; ++a)
+        for (int b = a + 1; b < n; ++b)
+            if (buf[a] && buf[b] && overlap(buf[a], len[a], buf[b], len[b]))
+                return fail("%s: aliased buffers", me);
+    return 0;
 }
 
 // The host refusals the three cg entries share: the length and the count of partial sums that a
@@ -1119,132 +1135,124 @@ static PdDesc pd_desc(int nr, int ne, int na, int wrap_a, int has_r, int has_e, 
                   has_a && na > 1, wrap_a && na > 1};
 }
 
-// sphrt_pd_primal_f64 and sphrt_dp_primal_f64: one step behind `tau`, or one per voxel.
-static int pd_primal_entry(const char* me, bool per_voxel, const double* x, const double* g,
-                           const double* q, double* x_new, int nr, int ne, int na, int wrap_a,
-                           int has_r, int has_e, int has_a, double c_damp, const double* tau,
-                           double lower, double upper, double* part_mm, void* stream) {
+// include/sphrt_iso.h: the weights' refusal the two entries share (a NaN fails the compare).
+static int refuse_iso_weights(const char* me, const double* w) {
+    for (int ax = 0; ax < 3; ++ax)
+        if (!(w[ax] >= 0.0) || __builtin_isinf(w[ax]))
+            return fail("%s: the weights w_ax must be finite and >= 0, not %g", me, w[ax]);
+    return 0;
+}
+
+// sphrt_pd_primal_f64, sphrt_dp_primal_f64 (per_voxel: one step per voxel behind `tau`, not one)
+// and sphrt_iso_primal_f64 (w: the three weights, null for the other two).
+static int pd_primal_entry(const char* me, bool per_voxel, const double* w, const double* x,
+                           const double* g, const double* q, double* x_new, int nr, int ne, int na,
+                           int wrap_a, int has_r, int has_e, int has_a, double c_damp,
+                           const double* tau, double lower, double upper, double* part_mm,
+                           void* stream) {
     int64_t n = 0;
     if (int e = refuse_pd(me, nr, ne, na, n)) return e;
     if (!x || !g || !q || !x_new || !tau || !part_mm) return fail("%s: null buffer", me);
+    if (w)
+        if (int e = refuse_iso_weights(me, w)) return e;
     if (lower != lower || upper != upper || !(lower < upper))
         return fail("%s: bounds need lower < upper, neither NaN (%g, %g)", me, lower, upper);
     const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
     const void* buf[6] = {x, g, x_new, q, part_mm, tau};
     const int64_t len[6] = {nb, nb, nb, 3 * nb, pb, per_voxel ? nb : (int64_t)sizeof(double)};
-    for (int a = 0; a < 6; ++a)
-        for (int b = a + 1; b < 6; ++b)
-            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
+    if (int e = refuse_aliased(me, buf, len, 6, 6)) return e;
     StreamGuard guard(stream);
     const PdDesc desc = pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a);
-    if (per_voxel)
-        hipLaunchKernelGGL(pd_primal_kernel<true>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                           (hipStream_t)stream, x, g, q, x_new, (uint32_t)n, desc, c_damp, tau,
-                           lower, upper, part_mm);
+    const dim3 grid(loss_grid(n)), block(kLossThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (w)
+        hipLaunchKernelGGL((pd_primal_kernel<false, true>), grid, block, 0, st, x, g, q, x_new,
+                           (uint32_t)n, desc, c_damp, tau, lower, upper, part_mm, w[0], w[1], w[2]);
+    else if (per_voxel)
+        hipLaunchKernelGGL(pd_primal_kernel<true>, grid, block, 0, st, x, g, q, x_new, (uint32_t)n,
+                           desc, c_damp, tau, lower, upper, part_mm);
     else
-        hipLaunchKernelGGL(pd_primal_kernel<false>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                           (hipStream_t)stream, x, g, q, x_new, (uint32_t)n, desc, c_damp, tau,
-                           lower, upper, part_mm);
-    return check_launch(per_voxel ? "dp_primal" : "pd_primal");
+        hipLaunchKernelGGL(pd_primal_kernel<false>, grid, block, 0, st, x, g, q, x_new,
+                           (uint32_t)n, desc, c_damp, tau, lower, upper, part_mm);
+    return check_launch(w ? "iso_primal" : per_voxel ? "dp_primal" : "pd_primal");
 }
 
 extern "C" int sphrt_pd_primal_f64(const double* x, const double* g, const double* q,
                                    double* x_new, int nr, int ne, int na, int wrap_a, int has_r,
                                    int has_e, int has_a, double c_damp, const double* tau,
                                    double lower, double upper, double* part_mm, void* stream) {
-    return pd_primal_entry("sphrt_pd_primal_f64", false, x, g, q, x_new, nr, ne, na, wrap_a, has_r,
-                           has_e, has_a, c_damp, tau, lower, upper, part_mm, stream);
+    return pd_primal_entry("sphrt_pd_primal_f64", false, nullptr, x, g, q, x_new, nr, ne, na,
+                           wrap_a, has_r, has_e, has_a, c_damp, tau, lower, upper, part_mm, stream);
 }
 
 extern "C" int sphrt_dp_primal_f64(const double* x, const double* g, const double* q,
                                    double* x_new, int nr, int ne, int na, int wrap_a, int has_r,
                                    int has_e, int has_a, double c_damp, const double* tau,
                                    double lower, double upper, double* part_mm, void* stream) {
-    return pd_primal_entry("sphrt_dp_primal_f64", true, x, g, q, x_new, nr, ne, na, wrap_a, has_r,
-                           has_e, has_a, c_damp, tau, lower, upper, part_mm, stream);
-}
-
-extern "C" int sphrt_pd_dual_f64(const double* x_new, const double* x_old, double* q, int nr,
-                                 int ne, int na, int wrap_a, int has_r, int has_e, int has_a,
-                                 double c_r, double c_e, double c_a, const double* sigma,
-                                 double* part_qq, void* stream) {
-    const char* me = "sphrt_pd_dual_f64";
-    int64_t n = 0;
-    if (int e = refuse_pd(me, nr, ne, na, n)) return e;
-    if (!x_new || !x_old || !q || !sigma || !part_qq) return fail("%s: null buffer", me);
-    for (double c : {c_r, c_e, c_a})
-        if (!(c >= 0.0) || __builtin_isinf(c))             // (a NaN fails the compare)
-            return fail("%s: the clamps c_ax must be finite and >= 0, not %g", me, c);
-    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
-    const void* buf[5] = {x_new, x_old, q, part_qq, sigma};
-    const int64_t len[5] = {nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
-    for (int a = 0; a < 5; ++a)
-        for (int b = a + 1; b < 5; ++b)
-            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
-    StreamGuard guard(stream);
-    hipLaunchKernelGGL(pd_dual_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                       (hipStream_t)stream, x_new, x_old, q, (uint32_t)n,
-                       pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a), c_r, c_e, c_a, sigma,
-                       part_qq);
-    return check_launch("pd_dual");
-}
-
-// include/sphrt_iso.h: the weights' refusal the two entries share (a NaN fails the compare).
-static int refuse_iso_weights(const char* me, double w_r, double w_e, double w_a) {
-    for (double w : {w_r, w_e, w_a})
-        if (!(w >= 0.0) || __builtin_isinf(w))
-            return fail("%s: the weights w_ax must be finite and >= 0, not %g", me, w);
-    return 0;
+    return pd_primal_entry("sphrt_dp_primal_f64", true, nullptr, x, g, q, x_new, nr, ne, na,
+                           wrap_a, has_r, has_e, has_a, c_damp, tau, lower, upper, part_mm, stream);
 }
 
 extern "C" int sphrt_iso_primal_f64(const double* x, const double* g, const double* q,
                                     double* x_new, int nr, int ne, int na, int wrap_a, double w_r,
                                     double w_e, double w_a, double c_damp, const double* tau,
                                     double lower, double upper, double* part_mm, void* stream) {
-    const char* me = "sphrt_iso_primal_f64";
+    const double w[3] = {w_r, w_e, w_a};
+    return pd_primal_entry("sphrt_iso_primal_f64", false, w, x, g, q, x_new, nr, ne, na, wrap_a,
+                           w_r > 0.0, w_e > 0.0, w_a > 0.0, c_damp, tau, lower, upper, part_mm,
+                           stream);
+}
+
+// sphrt_pd_dual_f64 (ax: the clamps c_ax) and sphrt_iso_dual_f64 (iso: ax the weights, and the
+// ball's radius).
+static int pd_dual_entry(const char* me, bool iso, const double* x_new, const double* x_old,
+                         double* q, int nr, int ne, int na, int wrap_a, int has_r, int has_e,
+                         int has_a, const double* ax, double radius, const double* sigma,
+                         double* part_qq, void* stream) {
     int64_t n = 0;
     if (int e = refuse_pd(me, nr, ne, na, n)) return e;
-    if (!x || !g || !q || !x_new || !tau || !part_mm) return fail("%s: null buffer", me);
-    if (int e = refuse_iso_weights(me, w_r, w_e, w_a)) return e;
-    if (lower != lower || upper != upper || !(lower < upper))
-        return fail("%s: bounds need lower < upper, neither NaN (%g, %g)", me, lower, upper);
+    if (!x_new || !x_old || !q || !sigma || !part_qq) return fail("%s: null buffer", me);
+    if (iso) {
+        if (int e = refuse_iso_weights(me, ax)) return e;
+        if (!(radius >= 0.0) || __builtin_isinf(radius))
+            return fail("%s: the radius must be finite and >= 0, not %g", me, radius);
+    } else {
+        for (int k = 0; k < 3; ++k)
+            if (!(ax[k] >= 0.0) || __builtin_isinf(ax[k]))         // (a NaN fails the compare)
+                return fail("%s: the clamps c_ax must be finite and >= 0, not %g", me, ax[k]);
+    }
     const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
-    const void* buf[6] = {x, g, x_new, q, part_mm, tau};
-    const int64_t len[6] = {nb, nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
-    for (int a = 0; a < 6; ++a)
-        for (int b = a + 1; b < 6; ++b)
-            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
+    const void* buf[5] = {x_new, x_old, q, part_qq, sigma};
+    const int64_t len[5] = {nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
+    if (int e = refuse_aliased(me, buf, len, 5, 5)) return e;
     StreamGuard guard(stream);
-    hipLaunchKernelGGL((pd_primal_kernel<false, true>), dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                       (hipStream_t)stream, x, g, q, x_new, (uint32_t)n,
-                       pd_desc(nr, ne, na, wrap_a, w_r > 0.0, w_e > 0.0, w_a > 0.0), c_damp, tau,
-                       lower, upper, part_mm, w_r, w_e, w_a);
-    return check_launch("iso_primal");
+    const PdDesc desc = pd_desc(nr, ne, na, wrap_a, has_r, has_e, has_a);
+    const dim3 grid(loss_grid(n)), block(kLossThreads);
+    if (iso)
+        hipLaunchKernelGGL(iso_dual_kernel, grid, block, 0, (hipStream_t)stream, x_new, x_old, q,
+                           (uint32_t)n, desc, ax[0], ax[1], ax[2], radius, sigma, part_qq);
+    else
+        hipLaunchKernelGGL(pd_dual_kernel, grid, block, 0, (hipStream_t)stream, x_new, x_old, q,
+                           (uint32_t)n, desc, ax[0], ax[1], ax[2], sigma, part_qq);
+    return check_launch(iso ? "iso_dual" : "pd_dual");
+}
+
+extern "C" int sphrt_pd_dual_f64(const double* x_new, const double* x_old, double* q, int nr,
+                                 int ne, int na, int wrap_a, int has_r, int has_e, int has_a,
+                                 double c_r, double c_e, double c_a, const double* sigma,
+                                 double* part_qq, void* stream) {
+    const double c[3] = {c_r, c_e, c_a};
+    return pd_dual_entry("sphrt_pd_dual_f64", false, x_new, x_old, q, nr, ne, na, wrap_a, has_r,
+                         has_e, has_a, c, 0.0, sigma, part_qq, stream);
 }
 
 extern "C" int sphrt_iso_dual_f64(const double* x_new, const double* x_old, double* q, int nr,
                                   int ne, int na, int wrap_a, double w_r, double w_e, double w_a,
                                   double radius, const double* sigma, double* part_qq,
                                   void* stream) {
-    const char* me = "sphrt_iso_dual_f64";
-    int64_t n = 0;
-    if (int e = refuse_pd(me, nr, ne, na, n)) return e;
-    if (!x_new || !x_old || !q || !sigma || !part_qq) return fail("%s: null buffer", me);
-    if (int e = refuse_iso_weights(me, w_r, w_e, w_a)) return e;
-    if (!(radius >= 0.0) || __builtin_isinf(radius))
-        return fail("%s: the radius must be finite and >= 0, not %g", me, radius);
-    const int64_t nb = n * (int64_t)sizeof(double), pb = (int64_t)loss_grid(n) * sizeof(double);
-    const void* buf[5] = {x_new, x_old, q, part_qq, sigma};
-    const int64_t len[5] = {nb, nb, 3 * nb, pb, (int64_t)sizeof(double)};
-    for (int a = 0; a < 5; ++a)
-        for (int b = a + 1; b < 5; ++b)
-            if (overlap(buf[a], len[a], buf[b], len[b])) return fail("%s: aliased buffers", me);
-    StreamGuard guard(stream);
-    hipLaunchKernelGGL(iso_dual_kernel, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                       (hipStream_t)stream, x_new, x_old, q, (uint32_t)n,
-                       pd_desc(nr, ne, na, wrap_a, w_r > 0.0, w_e > 0.0, w_a > 0.0), w_r, w_e,
-                       w_a, radius, sigma, part_qq);
-    return check_launch("iso_dual");
+    const double w[3] = {w_r, w_e, w_a};
+    return pd_dual_entry("sphrt_iso_dual_f64", true, x_new, x_old, q, nr, ne, na, wrap_a,
+                         w_r > 0.0, w_e > 0.0, w_a > 0.0, w, radius, sigma, part_qq, stream);
 }
 
 template <typename TY, bool PER_RAY>
@@ -1295,10 +1303,7 @@ static int cp_ray_dual_entry(const char* me, const double* z_new, const double* 
     const int64_t len[11] = {nb, nb, pb, pb, nb, nb, y_is_f64 ? nb : nb / 2, nb, nb,
                              PER_RAY ? nb : (int64_t)sizeof(double),
                              n * (int64_t)sizeof(int32_t)};
-    for (int a = 0; a < 4; ++a)                    // (an output against everything after it)
-        for (int b = a + 1; b < 11; ++b)
-            if (buf[a] && buf[b] && overlap(buf[a], len[a], buf[b], len[b]))
-                return fail("%s: aliased buffers", me);
+    if (int e = refuse_aliased(me, buf, len, 4, 11)) return e;   // (p, p_adj and the partial sums)
     StreamGuard guard(stream);
     hipStream_t st = (hipStream_t)stream;
     if (y_is_f64)
@@ -1350,10 +1355,7 @@ extern "C" int sphrt_dp_steps_f64(const double* col, const double* row, int64_t 
     const int64_t vb = n_vox * (int64_t)sizeof(double), rb = n_ray * (int64_t)sizeof(double);
     const void* buf[5] = {tau, sigma, col, row, order};
     const int64_t len[5] = {vb, rb, vb, rb, n_ray * (int64_t)sizeof(int32_t)};
-    for (int a = 0; a < 2; ++a)                    // (an output against everything after it)
-        for (int b = a + 1; b < 5; ++b)
-            if (buf[b] && overlap(buf[a], len[a], buf[b], len[b]))
-                return fail("%s: aliased buffers", me);
+    if (int e = refuse_aliased(me, buf, len, 2, 5)) return e;    // (tau and sigma)
     StreamGuard guard(stream);
     hipLaunchKernelGGL(dp_steps_kernel, dim3(loss_grid(n_vox > n_ray ? n_vox : n_ray)),
                        dim3(kLossThreads), 0, (hipStream_t)stream, col, row, (uint32_t)n_vox,

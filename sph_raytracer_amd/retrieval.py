@@ -1215,32 +1215,13 @@ def primal_dual(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=0.0
                          'solves the total without it)')
     if len(tvs) > 1:
         raise ValueError(f"{who} solves with one SmoothRegularizer(kind='abs'), not {len(tvs)}")
-    tv = (isos or tvs)[0]
-    cls, label = ('IsoTVRegularizer', 'IsoTVRegularizer') if isos else \
-        ('SmoothRegularizer', "SmoothRegularizer(kind='abs')")
-    if not tv.use_grad:
-        raise ValueError(f'{who}: {cls}(use_grad=False) is a monitor, not a term of '
-                         'the total')
-    if not _number(tv.lam) or not 0 < tv.lam < math.inf:
-        raise ValueError(f"{who} needs a finite scalar lam > 0 on {label}, "
-                         f'not lam = {tv.lam!r}')
-    if not _unit(tv.volume_mask):
-        raise ValueError(f"{who} does not take a volume_mask ({label})")
-    if not _unit(tv.projection_mask):
-        raise ValueError(f"{who}: the projection_mask of {label} must be 1")
+    term = (isos or tvs)[0]
+    label = 'IsoTVRegularizer' if isos else "SmoothRegularizer(kind='abs')"
+    _term_rules(who, term, type(term).__name__, label, f' on {label}, not lam = {term.lam!r}')
     bounds = _fista_args(lower, upper, lipschitz, power_iterations, who=who)
     if not _number(dual_ratio) or not 0 < dual_ratio < math.inf:
         raise ValueError(f'{who} needs a finite dual_ratio > 0, not {dual_ratio!r}')
-    shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
-    if len(shape) < 3:
-        raise ValueError(f'{who} needs a volume with axes (..., r, e, a), not shape {shape}')
-    if len(shape) > 3 and not isos and tv.time_weight > 0:
-        raise ValueError(f"{who}: SmoothRegularizer(kind='abs', time_weight={tv.time_weight!r}) "
-                         'on a volume with a time axis is not built (time_weight=0 is)')
-    if not any(_pd_axes(tv, shape)):
-        raise ValueError(f"{who}: {_tv_label(tv)} has no "
-                         f'edges on a volume of shape {shape} (an axis needs a weight > 0 and a '
-                         'length > 1)')
+    tv = _tv_on_volume(who, term, f, x0)
     bar = _Bar(range(num_iterations), progress_bar)
     run = _primal_dual_direct if _cg_is_direct(f, y, x0) else _primal_dual_generic
     return run(f, y, sq, smooth, tv, x0, num_iterations, float(damp), bounds[0], bounds[1],
@@ -1248,122 +1229,168 @@ def primal_dual(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=0.0
                float(dual_ratio), bar)
 
 
-def _pd_axes(tv, shape):
-    """[has_r, has_e, has_a]: which of the trailing axes of a volume of `shape` have edges."""
-    return [w > 0 and n > 1 for w, n in zip(tv.weights, shape[-3:])]
+def _term_rules(who, fn, cls, label, lam_text, rays=None):
+    """The rules `primal_dual` and `chambolle_pock` share for a term of their totals, in the order
+    both check them: a term of the total, a finite scalar lam > 0 (`lam_text`: the solver's own
+    end of that sentence), unit masks — but for a fidelity term, whose projection_mask may be a
+    tensor `gd`'s direct loop would weigh the residual with (`rays`: the measurements, then)."""
+    if not fn.use_grad:
+        raise ValueError(f'{who}: {cls}(use_grad=False) is a monitor, not a term of the total')
+    if not _number(fn.lam) or not 0 < fn.lam < math.inf:
+        raise ValueError(f'{who} needs a finite scalar lam > 0{lam_text}')
+    if not _unit(fn.volume_mask):
+        raise ValueError(f'{who} does not take a volume_mask ({label})')
+    if not _unit(fn.projection_mask) and not (rays is not None
+                                              and _ray_mask(fn.projection_mask, rays)):
+        raise ValueError(f'{who}: the projection_mask of {label} must be 1' + (
+            ' or a bool / float32 / float64 tensor on the device of y that broadcasts to '
+            'its shape' if rays is not None else ''))
 
 
-def _is_iso(tv):
-    return type(tv) is IsoTVRegularizer
+class _TVTerm:
+    """The TV term of `primal_dual` and `chambolle_pock` on a volume of `shape` over `f`, as the
+    refusals, the generic maps (`_tv_maps`) and the direct launches (`_tv_stage`) read it.  `term`:
+    a SmoothRegularizer(kind='abs'), an IsoTVRegularizer, or None (`chambolle_pock` without TV:
+    no axis has edges).
+
+        has      [has_r, has_e, has_a]: which of the trailing axes have edges
+        ring     the azimuth ring is closed (and longer than 1)
+        iso      the term is an IsoTVRegularizer: the weights sit in the differences and the dual
+                 is projected onto the ball of `radius` = lam / V; otherwise the differences are
+                 unweighted and axis ax is clamped to `clamps`[ax] = lam w_ax / V
+        bound    B / 4 of the difference operator, B >= |D|^2: the number of axes with edges, or
+                 for the iso term the sum of w_ax^2 over them (each 1-D difference operator's
+                 bound of 4, scaled by its weight and stacked)
+        label    the term as the refusals name it"""
+
+    def __init__(self, term, f, shape):
+        self.term, self.iso = term, type(term) is IsoTVRegularizer
+        self.weights = term.weights if term is not None else (0.0, 0.0, 0.0)
+        self.lam, self.n_vox = term.lam if term is not None else 0.0, math.prod(shape)
+        self.has = [w > 0 and n > 1 for w, n in zip(self.weights, shape[-3:])]
+        self.ring = bool(term is not None and len(shape) > 0 and shape[-1] > 1 and term.wraps(f))
+        self.bound = sum(w * w for w, h in zip(self.weights, self.has) if h) if self.iso \
+            else sum(self.has)
+        self.label = f'IsoTVRegularizer(weights={self.weights!r})' if self.iso \
+            else f"SmoothRegularizer(kind='abs', weights={self.weights!r})"
+
+    @property
+    def clamps(self):
+        return [self.lam * w / self.n_vox for w in self.weights]
+
+    @property
+    def radius(self):
+        return self.lam / self.n_vox
 
 
-def _tv_label(tv):
-    """The TV term as the refusals name it."""
-    if _is_iso(tv):
-        return f'IsoTVRegularizer(weights={tv.weights!r})'
-    return f"SmoothRegularizer(kind='abs', weights={tv.weights!r})"
+def _tv_on_volume(who, term, f, x0):
+    """The `_TVTerm` of `term` on the volume a solve from `x0` runs on (the grid's, or x0's own
+    shape); ValueError where that volume gives the term nothing to act on."""
+    shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
+    tv = _TVTerm(term, f, shape)
+    if term is None:
+        return tv
+    if len(shape) < 3:
+        raise ValueError(f'{who} needs a volume with axes (..., r, e, a), not shape {shape}')
+    if len(shape) > 3 and not tv.iso and term.time_weight > 0:
+        raise ValueError(f"{who}: SmoothRegularizer(kind='abs', time_weight={term.time_weight!r}) "
+                         'on a volume with a time axis is not built (time_weight=0 is)')
+    if not any(tv.has):
+        raise ValueError(f'{who}: {tv.label} has no edges on a volume of shape {shape} (an axis '
+                         'needs a weight > 0 and a length > 1)')
+    return tv
 
 
-def _tv_bound(tv, has):
-    """B / 4 of the TV term's difference operator, B >= |D|^2: the number of axes with edges
-    (kind='abs': the weights sit in the clamps, D is unweighted), or for an IsoTVRegularizer the
-    sum of w_ax^2 over them (each 1-D difference operator's bound of 4, scaled by its weight and
-    stacked)."""
-    if _is_iso(tv):
-        return sum(w * w for w, h in zip(tv.weights, has) if h)
-    return sum(has)
+def _clamp(u, a, b):
+    return t.where(u < a, a, t.where(u > b, b, u))
 
 
-def _tv_launches(tv, has, n_vox):
-    """(primal entry, TV-dual entry, the primal's axis arguments, the dual's axis arguments) of the
-    direct loops' two volume launches: include/sphrt_pd.h's with the has_* flags and the clamps
-    c_ax = lam w_ax / V, or for an IsoTVRegularizer include/sphrt_iso.h's with the weights and
-    the radius lam / V."""
-    if _is_iso(tv):
-        return ('sphrt_iso_primal_f64', 'sphrt_iso_dual_f64', list(tv.weights),
-                list(tv.weights) + [tv.lam / n_vox])
-    return ('sphrt_pd_primal_f64', 'sphrt_pd_dual_f64', list(has),
-            list(has) + [tv.lam * w / n_vox for w in tv.weights])
+def _start(f, x0, dev, lower, upper):
+    """(x_0, lower, upper) of the bounded loops: zeros on the grid (float64, on `dev`) or a copy of
+    `x0`, clamped into the bounds, and the bounds as 0-dim tensors beside it."""
+    x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=dev) if x0 is None \
+        else t.as_tensor(x0).detach().clone()
+    lo, hi = (t.full((), v, dtype=x.dtype, device=x.device) for v in (lower, upper))
+    return _clamp(x, lo, hi), lo, hi
+
+
+def _tv_stage(tv, shape, per_voxel=False):
+    """The two volume launches of the direct loops over a volume of `shape` = (nr, ne, na), bound
+    once -> (primal, dual):
+
+        primal(x, g, q, x_new, c, tau, lower, upper, part, stream)
+        dual(x_new, x, q, sigma, part, stream)
+
+    include/sphrt_pd.h's entries with the has_* flags and the clamps, for the iso term
+    include/sphrt_iso.h's with the weights and the radius; `per_voxel`: sphrt_dp_primal_f64 (tau
+    one step per voxel: include/sphrt_dp.h; never with the iso term).  Without a TV term the
+    primal launch gets zero flags — it never reads q then, but refuses a null or an overlapping
+    one — and `dual` launches nothing."""
+    from . import _lib
+    lib = _lib.load()
+    grid = (*shape, int(tv.ring))
+    if tv.iso:
+        p_name, d_name = 'sphrt_iso_primal_f64', 'sphrt_iso_dual_f64'
+        p_axes, d_axes = list(tv.weights), [*tv.weights, tv.radius]
+    else:
+        p_name = 'sphrt_dp_primal_f64' if per_voxel else 'sphrt_pd_primal_f64'
+        d_name = 'sphrt_pd_dual_f64'
+        p_axes = [int(h) for h in tv.has]
+        d_axes = p_axes + tv.clamps
+    p_entry, d_entry = getattr(lib, p_name), getattr(lib, d_name)
+
+    def primal(x, g, q, x_new, c, tau, lower, upper, part, stream):
+        _lib.check(p_entry(_lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), *grid, *p_axes,
+                           c, _lib.ptr(tau), lower, upper, _lib.ptr(part), stream), p_name)
+
+    def dual(x_new, x, q, sigma, part, stream):
+        if tv.term is not None:
+            _lib.check(d_entry(_lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), *grid, *d_axes,
+                               _lib.ptr(sigma), _lib.ptr(part), stream), d_name)
+    return primal, dual
 
 
 def _pd_steps(L, dual_ratio, n_axes):
     """(tau, sigma) as one-element tensors beside L: 1 / ((1 + ratio) L) and ratio L / B with
-    B = 4 n_axes (`_tv_bound`); both 0 when L is not > 0 (`_fista_step`'s rule for its step)."""
+    B = 4 n_axes (`_TVTerm.bound`); both 0 when L is not > 0 (`_fista_step`'s rule for its step)."""
     zero = t.zeros_like(L)
     tau = t.where(L > 0, 1.0 / ((1.0 + dual_ratio) * L), zero)
     sigma = t.where(L > 0, (dual_ratio * L) / (4.0 * n_axes), zero)
     return tau, sigma
 
 
-def _pd_info(mm, qq, L, tau, sigma, q):
-    """`primal_dual`'s info from MM_k and QQ_k (k = 0 .. K - 1) and the steps, on the host."""
-    mm0 = mm[0] if mm else 0.0
-    hist = [0.0 if v == 0 else math.sqrt(v / mm0) if mm0 > 0 else float('nan') for v in mm]
-    return {'primal_change': hist, 'dual_change': [math.sqrt(v) if v >= 0 else float('nan')
-                                                   for v in qq],
+def _change_history(mm, ref):
+    """[sqrt(MM_k / ref)], 0.0 where MM_k is exactly 0 (NaN where the reference is not > 0)."""
+    return [0.0 if v == 0 else math.sqrt(v / ref) if ref > 0 else float('nan') for v in mm]
+
+
+def _pd_info(mm, qq, L, tau, sigma, q, ref=None):
+    """`primal_dual`'s info from MM_k and QQ_k (k = 0 .. K - 1) and the steps, on the host (`ref`:
+    the MM the primal changes are relative to, MM_0 unless given)."""
+    if ref is None:
+        ref = mm[0] if mm else 0.0
+    return {'primal_change': _change_history(mm, ref),
+            'dual_change': [math.sqrt(v) if v >= 0 else float('nan') for v in qq],
             'lipschitz': L, 'tau': tau, 'sigma': sigma, 'dual': q}
 
 
-def _tv_generic(tv, f, x):
-    """The TV term's two maps in plain torch (narrow / roll differences) over volumes like `x`,
-    for `_primal_dual_generic` and `_chambolle_pock_generic` -> (has, adjoint, dual): which axes
-    have edges; adjoint(q) = D^T q; dual(q, xb, sigma) = the clamped dual step, a new tensor."""
-    n_vox = x.numel()
-    has, ring = _pd_axes(tv, x.shape), tv.wraps(f) and x.shape[-1] > 1
-    cax = [t.full((), tv.lam * w / n_vox, dtype=x.dtype, device=x.device) for w in tv.weights]
-
-    def clamp(u, a, b):
-        return t.where(u < a, a, t.where(u > b, b, u))
+def _tv_maps(tv, x):
+    """The TV term's two maps in plain torch (narrow / roll differences) over the r, e, a axes of
+    every slice of volumes like `x`, for `_primal_dual_generic` and `_chambolle_pock_generic`: the
+    specification of the launches of include/sphrt_pd.h and include/sphrt_iso.h and the CPU path
+    -> (adjoint, dual).  adjoint(q) = Dw^T q and dual(q, xb, sigma) = the dual step from
+    v = q + sigma Dw xb, a new tensor, with Dw_ax = w_ax D_ax.  kind='abs': w = 1 (no multiply;
+    an alpha of 1.0 is exact) and v_ax clamped to +-c_ax; the iso term: each voxel's triple v
+    projected onto the ball of radius lam / V (v itself where its norm is not greater; a slot
+    without an edge holds +0.0 and adds nothing to the norm)."""
+    has, wts = tv.has, tv.weights if tv.iso else (1.0, 1.0, 1.0)
+    cax = [t.full((), c, dtype=x.dtype, device=x.device) for c in tv.clamps]
+    radius = t.full((), tv.radius, dtype=x.dtype, device=x.device)
 
     def edges(v, ax):
         """The views (lower voxels, upper voxels) of `v` along axis ax, or None for the ring
         (every voxel has its edge: roll)."""
-        if ax == 2 and ring:
-            return None
-        n = v.shape[ax - 3]
-        return v.narrow(ax - 3, 0, n - 1), v.narrow(ax - 3, 1, n - 1)
-
-    def adjoint(q):
-        s = t.zeros_like(q[0])     # D^T q: the arriving edge, then the leaving one
-        for ax in range(3):
-            if not has[ax]:
-                continue
-            if edges(s, ax) is None:
-                s += t.roll(q[ax], 1, -1)
-                s -= q[ax]
-            else:
-                edges(s, ax)[1].add_(edges(q[ax], ax)[0])
-                edges(s, ax)[0].sub_(edges(q[ax], ax)[0])
-        return s
-
-    def dual(q, xb, sigma):
-        q_new = q.clone()
-        for ax in range(3):
-            if not has[ax]:
-                continue
-            if edges(xb, ax) is None:
-                v = t.addcmul(q[ax], t.roll(xb, -1, -1) - xb, sigma)
-                q_new[ax] = clamp(v, -cax[ax], cax[ax])
-            else:
-                below, above = edges(xb, ax)
-                v = t.addcmul(edges(q[ax], ax)[0], above - below, sigma)
-                edges(q_new[ax], ax)[0].copy_(clamp(v, -cax[ax], cax[ax]))
-        return q_new
-    return has, adjoint, dual
-
-
-def _iso_generic(tv, f, x):
-    """`_tv_generic` for an IsoTVRegularizer, over the r, e, a axes of every slice of volumes like
-    `x`: the specification of include/sphrt_iso.h's two launches and the CPU path -> (has,
-    adjoint, dual) with adjoint(q) = Dw^T q, Dw_ax = w_ax D_ax, and dual(q, xb, sigma) = each
-    voxel's triple q + sigma Dw xb projected onto the ball of radius lam / V (v itself where its
-    norm is not greater; a slot without an edge holds +0.0 and adds nothing to the norm)."""
-    has, ring = _pd_axes(tv, x.shape), tv.wraps(f) and x.shape[-1] > 1
-    radius = t.full((), tv.lam / x.numel(), dtype=x.dtype, device=x.device)
-    wts = tv.weights
-
-    def edges(v, ax):
-        if ax == 2 and ring:
+        if ax == 2 and tv.ring:
             return None
         n = v.shape[ax - 3]
         return v.narrow(ax - 3, 0, n - 1), v.narrow(ax - 3, 1, n - 1)
@@ -1381,17 +1408,7 @@ def _iso_generic(tv, f, x):
                 edges(s, ax)[0].sub_(edges(q[ax], ax)[0], alpha=wts[ax])
         return s
 
-    def dual(q, xb, sigma):
-        v = q.clone()
-        for ax in range(3):
-            if not has[ax]:
-                continue
-            if edges(xb, ax) is None:
-                v[ax] = t.addcmul(q[ax], wts[ax] * (t.roll(xb, -1, -1) - xb), sigma)
-            else:
-                below, above = edges(xb, ax)
-                edges(v[ax], ax)[0].copy_(
-                    t.addcmul(edges(q[ax], ax)[0], wts[ax] * (above - below), sigma))
+    def project(v):
         n2 = t.zeros_like(v[0])
         for ax in range(3):
             if has[ax]:
@@ -1400,12 +1417,21 @@ def _iso_generic(tv, f, x):
         outside = nrm > radius
         scale = radius / t.where(outside, nrm, t.ones_like(nrm))
         return t.where(outside, v * scale, v)
-    return has, adjoint, dual
 
-
-def _tv_maps(tv, f, x):
-    """(has, adjoint, dual) of the TV term of either class."""
-    return _iso_generic(tv, f, x) if _is_iso(tv) else _tv_generic(tv, f, x)
+    def dual(q, xb, sigma):
+        v = q.clone()
+        for ax in range(3):
+            if not has[ax]:
+                continue
+            if edges(xb, ax) is None:
+                d, q_ax, slot = t.roll(xb, -1, -1) - xb, q[ax], v[ax]
+            else:
+                below, above = edges(xb, ax)
+                d, q_ax, slot = above - below, edges(q[ax], ax)[0], edges(v[ax], ax)[0]
+            step = t.addcmul(q_ax, wts[ax] * d if tv.iso else d, sigma)
+            slot.copy_(step if tv.iso else _clamp(step, -cax[ax], cax[ax]))
+        return project(v) if tv.iso else v
+    return adjoint, dual
 
 
 def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, upper, lipschitz,
@@ -1415,27 +1441,19 @@ def _primal_dual_generic(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, 
     the CPU.  Every scalar stays a tensor on the device: no sync inside the loop."""
     with t.no_grad():
         yd = y.detach()
-        x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=yd.device) if x0 is None \
-            else t.as_tensor(x0).detach().clone()
-        n_vox = x.numel()
-        c = 2 * damp / n_vox
+        x, lo, hi = _start(f, x0, yd.device, lower, upper)
+        c = 2 * damp / x.numel()
         normal = _normal_generic(f, yd, sq, smooth, x)
-        has, tv_adjoint, tv_dual = _tv_maps(tv, f, x)
-        lo, hi = (t.full((), v, dtype=x.dtype, device=x.device) for v in (lower, upper))
-
-        def clamp(u, a, b):
-            return t.where(u < a, a, t.where(u > b, b, u))
-
+        tv_adjoint, tv_dual = _tv_maps(tv, x)
         L, _ = _fista_step(lambda v: t.add(normal(v, None), v, alpha=c), x, lipschitz,
                            power_iterations)
-        tau, sigma = _pd_steps(L, dual_ratio, _tv_bound(tv, has))
-        x = clamp(x, lo, hi)
+        tau, sigma = _pd_steps(L, dual_ratio, tv.bound)
         q = x.new_zeros((3,) + tuple(x.shape))
         mms, qqs = [], []
         try:
             for _ in bar:
                 gp = t.add(normal(x, yd), x, alpha=c)
-                x_new = clamp(t.addcmul(x, gp + tv_adjoint(q), -tau), lo, hi)
+                x_new = _clamp(t.addcmul(x, gp + tv_adjoint(q), -tau), lo, hi)
                 q_new = tv_dual(q, 2 * x_new - x, sigma)
                 mms.append(((x_new - x) ** 2).sum())
                 qqs.append(((q_new - q) ** 2).sum())
@@ -1463,25 +1481,16 @@ def _primal_dual_direct(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, u
     iteration (`_kernel_sum`).  Ctrl-C ends the loop after the last iteration whose dual launch
     went out: the x returned and info['dual'] are always the pair of one iteration."""
     from . import _lib
-    lib = _lib.load()
     dev, f64 = f._cdev, t.float64
     with t.no_grad(), t.cuda.device(dev):
-        x = t.zeros(tuple(f.grid.shape), dtype=f64, device=dev) if x0 is None \
-            else x0.detach().clone()
-        n_vox = x.numel()
-        nr, ne, na = x.shape
-        c = 2 * damp / n_vox
-        has = [int(h) for h in _pd_axes(tv, x.shape)]
-        ring = int(tv.wraps(f) and na > 1)
-        primal_name, dual_name, p_args, d_args = _tv_launches(tv, has, n_vox)
-        primal, dual = getattr(lib, primal_name), getattr(lib, dual_name)
+        x, _, _ = _start(f, x0, dev, lower, upper)
+        c = 2 * damp / x.numel()
+        primal, dual = _tv_stage(tv, x.shape)
         apply, pn = _normal_direct(f, y, sq, smooth, x)
         L, _ = _fista_step(lambda v: t.add(apply(v), v, alpha=c), x, lipschitz, power_iterations)
-        tau, sigma = _pd_steps(L, dual_ratio, _tv_bound(tv, has))
-        lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
-        x = t.where(x < lo, lo, t.where(x > hi, hi, x))
+        tau, sigma = _pd_steps(L, dual_ratio, tv.bound)
         x_new = t.empty_like(x)
-        q = t.zeros((3, nr, ne, na), dtype=f64, device=dev)
+        q = t.zeros((3,) + tuple(x.shape), dtype=f64, device=dev)
         rows = max(num_iterations, 1)
         part_mm = t.empty((rows, pn), dtype=f64, device=dev)
         part_qq = t.empty((rows, pn), dtype=f64, device=dev)
@@ -1492,13 +1501,8 @@ def _primal_dual_direct(f, y, sq, smooth, tv, x0, num_iterations, damp, lower, u
             for it in bar:
                 g = apply(x, True)
                 stream = _lib.stream_of(dev)
-                _lib.check(primal(
-                    _lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), nr, ne, na, ring,
-                    *p_args, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
-                    primal_name)
-                _lib.check(dual(
-                    _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring, *d_args,
-                    _lib.ptr(sigma), _lib.ptr(part_qq[it]), stream), dual_name)
+                primal(x, g, q, x_new, c, tau, lower, upper, part_mm[it], stream)
+                dual(x_new, x, q, sigma, part_qq[it], stream)
                 dual_out = it
                 x, x_new, done = x_new, x, it + 1      # (one statement: not separable)
         except KeyboardInterrupt:
@@ -1614,7 +1618,7 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
     operators, other dtypes, a non-contiguous x0 — runs the same algorithm in plain torch
     (`_chambolle_pock_generic`)."""
     who = 'chambolle_pock'
-    fid, tv = _cp_terms(y, loss_fns, damp, num_iterations, who)
+    fid, term = _cp_terms(y, loss_fns, damp, num_iterations, who)
     bounds = _fista_args(lower, upper, None, power_iterations, who=who)
     if norm is not None and (not _number(norm) or not 0 < norm < math.inf):
         raise ValueError(f'{who} needs a finite norm > 0 (or None), not {norm!r}')
@@ -1626,22 +1630,11 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
     if precondition is not None and norm is not None:
         raise ValueError(f"{who}: precondition='diagonal' takes its steps from the operator's row "
                          f'and column sums, not from a norm (norm={norm!r})')
-    if precondition is not None and _is_iso(tv):
+    if precondition is not None and type(term) is IsoTVRegularizer:
         raise ValueError(f"{who}: precondition='diagonal' with an IsoTVRegularizer is not built "
                          '(per-row steps do not fit a prox that couples three rows; '
                          "SmoothRegularizer(kind='abs') and precondition=None are)")
-    if tv is not None:
-        shape = tuple(f.grid.shape) if x0 is None else tuple(t.as_tensor(x0).shape)
-        if len(shape) < 3:
-            raise ValueError(f'{who} needs a volume with axes (..., r, e, a), not shape {shape}')
-        if len(shape) > 3 and not _is_iso(tv) and tv.time_weight > 0:
-            raise ValueError(f"{who}: SmoothRegularizer(kind='abs', time_weight="
-                             f'{tv.time_weight!r}) on a volume with a time axis is not built '
-                             '(time_weight=0 is)')
-        if not any(_pd_axes(tv, shape)):
-            raise ValueError(f"{who}: {_tv_label(tv)} has "
-                             f'no edges on a volume of shape {shape} (an axis needs a weight > 0 '
-                             'and a length > 1)')
+    tv = _tv_on_volume(who, term, f, x0)
     bar = _Bar(range(num_iterations), progress_bar)
     run = _chambolle_pock_direct if _cg_is_direct(f, y, x0) else _chambolle_pock_generic
     return run(f, y, fid, tv, x0, num_iterations, float(damp), bounds[0], bounds[1],
@@ -1650,8 +1643,7 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
 
 
 def _cp_terms(y, loss_fns, damp, num_iterations, who):
-    """(the fidelity term, the SmoothRegularizer(kind='abs') or None) of a total `chambolle_pock`
-    solves; ValueError naming what it does not, worded as `_cg_terms` words it."""
+    """(the fidelity term, the TV term or None) of a total `chambolle_pock` solves; ValueError naming what it does not, worded as `_cg_terms` words it."""
     if not isinstance(y, t.Tensor):
         raise ValueError(f'{who} needs measurements y as a tensor, not {type(y).__name__}')
     if not _number(damp) or not 0 <= damp < float('inf'):
@@ -1661,7 +1653,7 @@ def _cp_terms(y, loss_fns, damp, num_iterations, who):
         raise ValueError(f'{who} needs num_iterations as an integer >= 0, not {num_iterations!r}')
     fid = tv = None
     for fn in loss_fns:
-        name = type(fn).__name__
+        name, tv_iso = type(fn).__name__, type(tv) is IsoTVRegularizer
         if type(fn) in _FIDELITY:
             if fid is not None:
                 raise ValueError(f'{who} solves for one fidelity term, not two')
@@ -1671,15 +1663,15 @@ def _cp_terms(y, loss_fns, damp, num_iterations, who):
                 raise ValueError(f"{who} takes a smooth term as total variation only: "
                                  f"SmoothRegularizer(kind={fn.smooth_kind!r}) is not built "
                                  "(kind='abs' is)")
-            if _is_iso(tv):
+            if tv_iso:
                 raise ValueError(f"{who} solves with at most one TV term: a SmoothRegularizer("
                                  "kind='abs') beside an IsoTVRegularizer is not built")
             if tv is not None:
                 raise ValueError(f"{who} solves with at most one SmoothRegularizer(kind='abs'), "
                                  'not two')
             tv = fn
-        elif _is_iso(fn):
-            if _is_iso(tv):
+        elif type(fn) is IsoTVRegularizer:
+            if tv_iso:
                 raise ValueError(f'{who} solves with at most one IsoTVRegularizer, not two')
             if tv is not None:
                 raise ValueError(f"{who} solves with at most one TV term: an IsoTVRegularizer "
@@ -1689,16 +1681,8 @@ def _cp_terms(y, loss_fns, damp, num_iterations, who):
             raise ValueError(f'{who} needs a total of one SquareLoss, AbsLoss, HuberLoss or '
                              f"PoissonLoss and at most one SmoothRegularizer(kind='abs'): {name} "
                              'is neither (gd takes it)')
-        if not fn.use_grad:
-            raise ValueError(f'{who}: {name}(use_grad=False) is a monitor, not a term of the total')
-        if not _number(fn.lam) or not 0 < fn.lam < math.inf:
-            raise ValueError(f'{who} needs a finite scalar lam > 0, not {name}.lam = {fn.lam!r}')
-        if not _unit(fn.volume_mask):
-            raise ValueError(f'{who} does not take a volume_mask ({name})')
-        if not _unit(fn.projection_mask) and not (fn is fid and _ray_mask(fn.projection_mask, y)):
-            raise ValueError(f'{who}: the projection_mask of {name} must be 1' + (
-                ' or a bool / float32 / float64 tensor on the device of y that broadcasts to '
-                'its shape' if fn is fid else ''))
+        _term_rules(who, fn, name, name, f', not {name}.lam = {fn.lam!r}',
+                    rays=y if fn is fid else None)
     if fid is None:
         raise ValueError(f'{who} needs one SquareLoss, AbsLoss, HuberLoss or PoissonLoss among '
                          'loss_fns')
@@ -1761,12 +1745,9 @@ def _cp_steps(LA, n_axes, s_bar, c, dual_ratio):
 
 def _cp_info(mm, qq, pp, fid, LA, tau, sigma, q, p):
     """`chambolle_pock`'s info from the per-iteration sums and the steps, on the host."""
-    info = _pd_info(mm, qq, LA, tau, sigma, q)
     # (p_0 = 0: without damping the first step does not move x, so the reference is the first
     # MM_k that is not zero)
-    mm0 = next((v for v in mm if v > 0), 0.0)
-    info['primal_change'] = [0.0 if v == 0 else math.sqrt(v / mm0) if mm0 > 0 else float('nan')
-                             for v in mm]
+    info = _pd_info(mm, qq, LA, tau, sigma, q, ref=next((v for v in mm if v > 0), 0.0))
     info['norm'] = info.pop('lipschitz')
     info['ray_dual_change'] = [math.sqrt(v) if v >= 0 else float('nan') for v in pp]
     info['fidelity'] = fid
@@ -1812,8 +1793,7 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
     Every scalar stays a tensor on the device: no sync inside the loop."""
     with t.no_grad():
         yd = y.detach()
-        x = t.zeros(tuple(f.grid.shape), dtype=t.float64, device=yd.device) if x0 is None \
-            else t.as_tensor(x0).detach().clone()
+        x, lo, hi = _start(f, x0, yd.device, lower, upper)
         dshape, dtype, dev = tuple(x.shape), x.dtype, x.device
         pdt = t.promote_types(yd.dtype, dtype)
         m = yd.to(pdt)
@@ -1824,14 +1804,14 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
         w = None if _unit(fid.projection_mask) else \
             fid.projection_mask.detach().to(pdt).expand(yd.shape)
         s = t.full_like(m, s_bar) if w is None else s_bar * w
-        lo, hi = (t.full((), v, dtype=dtype, device=dev) for v in (lower, upper))
-        has, tv_adjoint, tv_dual = _tv_maps(tv, f, x) if tv is not None else ([], None, None)
+        with_tv = tv.term is not None
+        tv_adjoint, tv_dual = _tv_maps(tv, x)
         if diagonal:
             # row and column sums of A >= 0: one forward and one adjoint of ones
             rho_s = dual_ratio * s_bar
             row = f(t.ones_like(x)).to(pdt)
             col = f._apply_adjoint(t.ones_like(m), dshape, dtype, dev)
-            deg = _dp_degree(has, tv.wraps(f) and dshape[-1] > 1, x) if tv is not None else 0.0
+            deg = _dp_degree(tv.has, tv.ring, x) if with_tv else 0.0
             tau, sigma = _dp_steps(row, col, deg, rho_s, c)
             sigma_tv = t.full((), rho_s / 2, dtype=dtype, device=dev)
             LA = t.zeros(1, dtype=dtype, device=dev)
@@ -1839,10 +1819,9 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
             # |A|^2: v -> A^T(A v) is `_normal_generic` of a SquareLoss whose factor 2 lam / M is 1
             ata = _normal_generic(f, yd, SquareLoss(lam=n_meas / 2), None, x)
             LA, _ = _fista_step(lambda v: ata(v, None), x, norm, power_iterations)
-            tau, sigma = _cp_steps(LA, _tv_bound(tv, has), s_bar, c, dual_ratio)
+            tau, sigma = _cp_steps(LA, tv.bound, s_bar, c, dual_ratio)
             sigma_tv = sigma
-        x = t.where(x < lo, lo, t.where(x > hi, hi, x))
-        q = x.new_zeros((3,) + dshape) if tv is not None else None
+        q = x.new_zeros((3,) + dshape) if with_tv else None
         z = f(x)
         p = t.zeros_like(m)
         mms, qqs, pps, fids, done = [], [], [], [], 0
@@ -1850,18 +1829,17 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
             for _ in bar:
                 g = f._apply_adjoint(p, dshape, dtype, dev)
                 gp = t.add(g, x, alpha=c)
-                if tv is not None:
+                if with_tv:
                     gp = gp + tv_adjoint(q)
-                u = t.addcmul(x, gp, -tau)
-                x_new = t.where(u < lo, lo, t.where(u > hi, hi, u))
-                q_new = tv_dual(q, 2 * x_new - x, sigma_tv) if tv is not None else None
+                x_new = _clamp(t.addcmul(x, gp, -tau), lo, hi)
+                q_new = tv_dual(q, 2 * x_new - x, sigma_tv) if with_tv else None
                 z_new = f(x_new)
                 p_new = _cp_prox(kind, par, t.addcmul(p, 2 * z_new - z, sigma), sigma, s, m)
                 rho = _cp_rho(kind, par, z_new.to(pdt), m)
                 fids.append(s_bar * (rho if w is None else w * rho).sum())
                 mms.append(((x_new - x) ** 2).sum())
                 pps.append(((p_new - p) ** 2).sum())
-                if tv is not None:
+                if with_tv:
                     qqs.append(((q_new - q) ** 2).sum())
                 x, z, p, q, done = x_new, z_new, p_new, q_new, done + 1
         except KeyboardInterrupt:
@@ -1869,7 +1847,7 @@ def _chambolle_pock_generic(f, y, fid, tv, x0, num_iterations, damp, lower, uppe
         for sums in (mms, qqs, pps, fids):      # (Ctrl-C: the sums of an iteration not kept)
             del sums[done:]
         y_hat = f(x)
-        if tv is None:
+        if not with_tv:
             qqs = [LA.new_zeros(()) for _ in range(done)]
         sums = t.stack(mms + qqs + pps + fids).to(t.float64) if done \
             else LA.new_zeros(0).to(t.float64)
@@ -1920,11 +1898,10 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
     dev, f64 = f._cdev, t.float64
     fused = isinstance(f, MatrixFreeOperator)
     with t.no_grad(), t.cuda.device(dev):
-        x = t.zeros(tuple(f.grid.shape), dtype=f64, device=dev) if x0 is None \
-            else x0.detach().clone()
+        x, _, _ = _start(f, x0, dev, lower, upper)
         dshape = tuple(x.shape)
         n_vox = x.numel()
-        nr, ne, na = x.shape
+        with_tv = tv.term is not None
         c = 2 * damp / n_vox
         yd = y.detach().contiguous()
         n_meas = yd.numel()
@@ -1936,12 +1913,6 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
         else:
             w_ray = t.ones(n_meas, dtype=f64, device=dev)
             s_ray = t.full((n_meas,), s_bar, dtype=f64, device=dev)
-        if tv is not None:
-            has = [int(h) for h in _pd_axes(tv, x.shape)]
-            ring = int(tv.wraps(f) and na > 1)
-            cax = [tv.lam * w / n_vox for w in tv.weights]
-        else:
-            has, ring, cax = [0, 0, 0], 0, [0.0, 0.0, 0.0]
         if diagonal:
             pn = lib.sphrt_loss_partials(n_vox)
             LA = t.zeros(1, dtype=f64, device=dev)
@@ -1951,7 +1922,7 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
             ata, pn = _normal_direct(f, y, SquareLoss(lam=n_meas / 2), None, x)
             LA, _ = _fista_step(ata, x, norm, power_iterations)
             del ata
-            tau, sigma = _cp_steps(LA, _tv_bound(tv, has), s_bar, c, dual_ratio)
+            tau, sigma = _cp_steps(LA, tv.bound, s_bar, c, dual_ratio)
             sigma_tv = sigma
         ps = lib.sphrt_loss_partials(n_meas)
         y_ray, order, res_order, loop_desc, positions, keep = yd.reshape(-1), None, None, None, \
@@ -2000,27 +1971,18 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
             col = adjoint(t.ones(n_meas, dtype=f64, device=dev))
             tau, sigma = t.empty_like(x), t.empty(n_meas, dtype=f64, device=dev)
             _lib.check(lib.sphrt_dp_steps_f64(
-                _lib.ptr(col), _lib.ptr(row), n_meas, nr, ne, na, ring, *has, rho, c,
+                _lib.ptr(col), _lib.ptr(row), n_meas, *dshape, int(tv.ring),
+                *(int(h) for h in tv.has), rho, c,
                 _lib.ptr(order if positions else None), _lib.ptr(tau), _lib.ptr(sigma),
                 _lib.stream_of(dev)), 'sphrt_dp_steps_f64')
             del row, col
             sigma_tv = t.full((1,), rho / 2, dtype=f64, device=dev)
-        primal, ray_dual = (lib.sphrt_dp_primal_f64, lib.sphrt_dp_ray_dual_f64) if diagonal \
-            else (lib.sphrt_pd_primal_f64, lib.sphrt_cp_ray_dual_f64)
-        primal_name, ray_dual_name = ('sphrt_dp_primal_f64', 'sphrt_dp_ray_dual_f64') if diagonal \
-            else ('sphrt_pd_primal_f64', 'sphrt_cp_ray_dual_f64')
-        p_args, d_args, tv_dual, tv_dual_name = has, has + cax, lib.sphrt_pd_dual_f64, \
-            'sphrt_pd_dual_f64'
-        if _is_iso(tv):        # (never with `diagonal`: refused by chambolle_pock)
-            primal_name, tv_dual_name, p_args, d_args = _tv_launches(tv, has, n_vox)
-            primal, tv_dual = getattr(lib, primal_name), getattr(lib, tv_dual_name)
-
-        lo, hi = (t.full((), v, dtype=f64, device=dev) for v in (lower, upper))
-        x = t.where(x < lo, lo, t.where(x > hi, hi, x))
+        primal, tv_dual = _tv_stage(tv, dshape, per_voxel=diagonal)
+        ray_dual_name = 'sphrt_dp_ray_dual_f64' if diagonal else 'sphrt_cp_ray_dual_f64'
+        ray_dual = getattr(lib, ray_dual_name)
         x_new = t.empty_like(x)
-        # (without TV the primal launch never reads q, has_* being 0, but refuses a null or an
-        # overlapping one: the buffer stays, untouched)
-        q = t.zeros((3, nr, ne, na), dtype=f64, device=dev)
+        # (without TV the primal launch never reads q, but wants the buffer: it stays, untouched)
+        q = t.zeros((3,) + dshape, dtype=f64, device=dev)
         rows = max(num_iterations, 1)
         part_mm = t.empty((rows, pn), dtype=f64, device=dev)
         part_qq = t.zeros((rows, pn), dtype=f64, device=dev)
@@ -2038,16 +2000,9 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
                 stream = _lib.stream_of(dev)
                 if stage == 0:
                     g = adjoint()
-                    _lib.check(primal(
-                        _lib.ptr(x), _lib.ptr(g), _lib.ptr(q), _lib.ptr(x_new), nr, ne, na, ring,
-                        *p_args, c, _lib.ptr(tau), lower, upper, _lib.ptr(part_mm[it]), stream),
-                        primal_name)
+                    primal(x, g, q, x_new, c, tau, lower, upper, part_mm[it], stream)
                 elif stage == 1:
-                    if tv is not None:
-                        _lib.check(tv_dual(
-                            _lib.ptr(x_new), _lib.ptr(x), _lib.ptr(q), nr, ne, na, ring,
-                            *d_args, _lib.ptr(sigma_tv), _lib.ptr(part_qq[it]), stream),
-                            tv_dual_name)
+                    tv_dual(x_new, x, q, sigma_tv, part_qq[it], stream)
                 elif stage == 2:
                     zn = forward(x_new, z_new)
                 else:
@@ -2067,7 +2022,7 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
             # launch) nothing has been written in place, and the iteration is dropped; after it,
             # q (or p) is one step ahead of x: the remaining steps go out, so that the x, q and p
             # returned belong to one iteration
-            if done < num_iterations and stage >= (2 if tv is not None else 4):
+            if done < num_iterations and stage >= (2 if with_tv else 4):
                 advance(done)
                 x, x_new, z, z_new, done, stage = x_new, x, zn, z, done + 1, 0
         y_hat = f(x)       # (goes out before the readback waits)
@@ -2085,7 +2040,7 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
         if diagonal:
             return x, y_hat, _dp_info(
                 _cp_info(host[:done], host[done:2 * done], host[2 * done:3 * done], fids, None,
-                         None, None, q if tv is not None else None, p.view(yd.shape)),
+                         None, None, q if with_tv else None, p.view(yd.shape)),
                 tau, sigma.view(yd.shape), rho / 2)
     return x, y_hat, _cp_info(host[:done], host[done:2 * done], host[2 * done:3 * done], fids,
-                              *host[-3:], q if tv is not None else None, p.view(yd.shape))
+                              *host[-3:], q if with_tv else None, p.view(yd.shape))

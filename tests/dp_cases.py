@@ -254,3 +254,62 @@ def golden_arrays(**kw):
         keys = GOLDEN_HISTORIES[:3] if case[1] == 'poisson' else GOLDEN_HISTORIES
         out[key + '/hist'] = np.array([info[k] for k in keys])
     return out
+
+
+# The generic paths the record above does not reach — `primal_dual` with either TV term,
+# `chambolle_pock` with the iso term and with precondition='diagonal' — recorded the same way
+# (this repository's own run, under `ieee_sqrt`, without the Poisson kind's fidelity history) from
+# the commit before the TV term's plumbing was folded into one description, one pair of generic
+# maps and one direct stage: tests/golden/tv_paths_bits.npz.  The inputs hold nothing a host's
+# libraries decide: the problems are test_pd_cpu's and cp_cases' 'tiny' ones, the damping is the
+# constant cp_cases.DAMP (not the eigenvalue-derived one of the certificate tests).
+TV_GOLDEN_FILE = 'tv_paths_bits.npz'
+TV_GOLDEN_CASES = [c for c in cp.solver_cases() if c[0] == 'tiny']
+# (masked, the square smooth term's wrap_a) of pd_cases.VARIANTS: the smallest problem without a
+# smooth term and the TV ring closed, and with one and the ring open
+TV_GOLDEN_VARIANTS = [pc.VARIANTS[0], pc.VARIANTS[3]]
+
+
+def tv_golden_arrays():
+    """{path + case id + '/x' | '/q' | '/p' | '/hist' | '/steps' | '/tau' | '/sigma': array} of the
+    generic paths on the CPU under `ieee_sqrt`, GOLDEN_ITERATIONS iterations each: 'pd-abs-' and
+    'pd-iso-' (`primal_dual` on TV_GOLDEN_VARIANTS), 'cp-iso-' (`chambolle_pock` with the iso term
+    on the TV cases of TV_GOLDEN_CASES) and 'cp-diag-' (precondition='diagonal' on all of them)."""
+    import iso_cases as ic
+    from sph_raytracer_amd.retrieval import primal_dual
+    from test_pd_cpu import _operator, quadratic_terms, tv_term
+    out = {}
+    op, y, mask = _operator('tiny')
+    for masked, wrap in TV_GOLDEN_VARIANTS:
+        for name, tv in (('abs', tv_term(masked)), ('iso', ic.tv_term(pc.tv_wrap(masked)))):
+            with ieee_sqrt() as calls:
+                x, _, info = primal_dual(op, y, quadratic_terms(mask, masked, wrap) + [tv],
+                                         damp=cp.DAMP, lower=pc.LOWER, upper=pc.UPPER,
+                                         num_iterations=GOLDEN_ITERATIONS)
+            # (the ball projection takes one square root per iteration, the clamp none)
+            assert calls[0] >= GOLDEN_ITERATIONS if name == 'iso' else calls[0] == 0, calls
+            key = f'pd-{name}-{"masked" if masked else "unit"}-{wrap}'
+            out[key + '/x'], out[key + '/q'] = x.numpy(), info['dual'].numpy()
+            out[key + '/hist'] = np.array([info[k] for k in GOLDEN_HISTORIES[:2]])
+            out[key + '/steps'] = np.array([info[k] for k in ('lipschitz', 'tau', 'sigma')])
+    for case in TV_GOLDEN_CASES:
+        keys = GOLDEN_HISTORIES[:3] if case[1] == 'poisson' else GOLDEN_HISTORIES
+        runs = [('cp-diag-', lambda: solve_case(case, iterations=GOLDEN_ITERATIONS))]
+        if case[2]:
+            runs.append(('cp-iso-', lambda: ic.cp_solve(case, iterations=GOLDEN_ITERATIONS)))
+        for path, run in runs:
+            with ieee_sqrt() as calls:
+                x, _, info = run()
+            if path == 'cp-iso-' or case[1] == 'poisson':
+                assert calls[0] >= GOLDEN_ITERATIONS, calls
+            key = path + cp.case_id(case)
+            out[key + '/x'], out[key + '/p'] = x.numpy(), info['ray_dual'].numpy()
+            if case[2]:
+                out[key + '/q'] = info['dual'].numpy()
+            out[key + '/hist'] = np.array([info[k] for k in keys])
+            if path == 'cp-diag-':
+                out[key + '/tau'], out[key + '/sigma'] = info['tau'].numpy(), info['sigma'].numpy()
+                out[key + '/steps'] = np.array([info['sigma_tv']])
+            else:
+                out[key + '/steps'] = np.array([info[k] for k in ('norm', 'tau', 'sigma')])
+    return out

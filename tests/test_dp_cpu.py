@@ -346,6 +346,21 @@ def test_precondition_none_gives_the_recorded_bits():
     assert not any(np.array_equal(other[k], want[k]) for k in want.files if k.endswith('/x'))
 
 
+def test_the_tv_paths_give_the_recorded_bits():
+    """`primal_dual` with the abs and the iso term, `chambolle_pock` with the iso term and with
+    precondition='diagonal': x, the duals, the histories and the steps of
+    dp_cases.tv_golden_arrays, bit for bit against the values recorded before the TV term's
+    plumbing was folded (tests/golden/tv_paths_bits.npz; the same rules as the record above)."""
+    want = np.load(os.path.join(ROOT, 'tests', 'golden', dc.TV_GOLDEN_FILE))
+    got = dc.tv_golden_arrays()
+    assert sorted(got) == sorted(want.files)
+    paths = {k.split('-')[0] + '-' + k.split('-')[1] for k in got}
+    assert paths == {'pd-abs', 'pd-iso', 'cp-iso', 'cp-diag'}
+    for key, v in got.items():
+        assert v.dtype == np.float64 and v.shape == want[key].shape, key
+        assert np.array_equal(v.view(np.int64), want[key].view(np.int64)), key
+
+
 def test_other_inputs_solve_on_the_generic_path():
     """A float32 start runs in its dtype, zero iterations return the clamped start with the
     steps, and a dynamic operator (TV over each slice's r, e, a) closes its own gap."""
