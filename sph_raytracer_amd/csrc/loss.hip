@@ -6,7 +6,11 @@
 // mean absolute negative part and -lam/N on the gradient of every negative voxel.  Through torch
 // that is ~9 elementwise launches plus two mean reductions (a memset and a reduce each) of
 // 5-9 us on a 64^3 problem; here it is two launches, each leaving its workgroups' partial sums
-// of the loss (summed for every iteration at once after the loop).
+// of the loss (summed for every iteration at once after the loop).  The residual launch is one
+// kernel, residual_kernel, for every fidelity term — a masked SquareLoss, AbsLoss, HuberLoss and
+// PoissonLoss beside the plain one: a term is a small policy struct (SqFid .. PoissonFid) that
+// gives the adjoint's input and the loss's share per ray, its penalty from the rho_* helpers the
+// ray dual below shares, behind the four C entries and one host helper (residual_launch).
 //
 // The elementwise values are single IEEE operations, the ones torch's elementwise ops give (the
 // library is built with -ffp-contract=off), so the gradient and hence the iterates stay bitwise
@@ -50,91 +54,91 @@ __device__ __forceinline__ void block_partial(double v, double* out) {
     }
 }
 
-// r = yhat - y (y float32 or float64, promoted exactly); r_scaled = r * scale; partial sums of
-// r * r.  With `order` (a trace's row -> geometry ray map), r_scaled[j] is the residual of ray
-// order[j]: the transposed adjoint's input in trace order, without a separate permutation.
-template <typename TY>
-__global__ __launch_bounds__(kLossThreads) void sq_residual_kernel(
-    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n, double scale,
-    const int32_t* __restrict__ order, double* __restrict__ r_scaled, double* __restrict__ part) {
-    double acc = 0.0;
-    for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
-         j += (int64_t)gridDim.x * kLossThreads) {
-        const int64_t i = order ? (int64_t)order[j] : j;
-        const double r = yhat[i] - (double)y[i];
-        r_scaled[j] = r * scale;
-        acc += r * r;
-    }
-    block_partial(acc, part);
+// The per-ray penalty rho of the fidelity terms, written once: the residual policies below and
+// cp_ray_dual_kernel both call these, so their sums are op for op the same.
+// Square: r * r.  Abs: |r|.  Huber (delta > 0): with z = |r|, z < delta ? (0.5 * z) * z :
+// delta * (z - 0.5 * delta) — torch's huber_loss forward, operation by operation (a NaN residual
+// fails the compare and stays NaN).  Poisson: p - m * log(q) with q = p + eps formed by the caller
+// (one rounding) — torch's poisson_nll_loss forward, the device's log; no guards: q <= 0 gives
+// NaN or -+inf as in torch.
+__device__ __forceinline__ double rho_square(double r) { return r * r; }
+__device__ __forceinline__ double rho_abs(double r) { return __builtin_fabs(r); }
+__device__ __forceinline__ double rho_huber(double r, double delta) {
+    const double z = __builtin_fabs(r);
+    return z < delta ? (0.5 * z) * z : delta * (z - 0.5 * delta);
+}
+__device__ __forceinline__ double rho_poisson(double p, double q, double m) {
+#pragma clang fp contract(off)
+    const double t = m * log(q);
+    return p - t;
 }
 
-// The same with per-element factors (SquareLoss(projection_mask=w): lam * mean(w * (y - f(d))^2)):
-// r_scaled[j] = r * ray_scale[i] (i = order[j], as y) and partial sums of weight[i] * (r * r) —
-// two roundings, the order torch's mask * (y - f)**2 takes.  The same grid, strides and tree.
-template <typename TY>
-__global__ __launch_bounds__(kLossThreads) void wsq_residual_kernel(
-    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n,
-    const double* __restrict__ ray_scale, const double* __restrict__ weight,
-    const int32_t* __restrict__ order, double* __restrict__ r_scaled, double* __restrict__ part) {
-    double acc = 0.0;
-    for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
-         j += (int64_t)gridDim.x * kLossThreads) {
-        const int64_t i = order ? (int64_t)order[j] : j;
-        const double r = yhat[i] - (double)y[i];
-        r_scaled[j] = r * ray_scale[i];
-        acc += weight[i] * (r * r);
+// A fidelity term as residual_kernel sees it: at(p, m, i, term) returns the adjoint's input for
+// the forward value p and the measurement m of ray i and leaves the ray's share of the loss in
+// `term`; null() is the host's refusal of a missing per-ray array.
+//   SqFid      SquareLoss, lam * mean((y - f(d))^2): r * scale, and r * r.
+//   WsqFid     SquareLoss(projection_mask=w): r * ray_scale[i], and weight[i] * (r * r) — two
+//              roundings, the order torch's mask * (y - f)**2 takes.
+//   RobustFid  AbsLoss (delta == 0) and HuberLoss (delta > 0): psi(r) * ray_scale[i] (robust_psi,
+//              common.hpp: the sign of r, or r clamped to +-delta), and weight[i] * rho(r).
+//   PoissonFid PoissonLoss, lam * mean(w * (p - y * log(p + eps))): with q = p + eps,
+//              ray_scale[i] + ((-ray_scale[i]) * m) / q (poisson_weight, common.hpp: autograd's
+//              gradient at p for an incoming ray_scale[i]), and weight[i] * (p - m * log(q)).
+struct SqFid {
+    double scale;
+    bool null() const { return false; }
+    __device__ __forceinline__ double at(double p, double m, int64_t, double& term) const {
+        const double r = p - m;
+        term = rho_square(r);
+        return r * scale;
     }
-    block_partial(acc, part);
-}
-
-// The robust tails (AbsLoss: lam * mean(w * |y - f(d)|); HuberLoss: lam * mean(w * huber(f(d),
-// y))): r_scaled[j] = psi(r) * ray_scale[i] (robust_psi, common.hpp: the sign of r, or r clamped
-// to +-delta) and partial sums of weight[i] * |r| (delta == 0, ABS) or weight[i] * h(r) with
-// z = |r|, h = z < delta ? (0.5 * z) * z : delta * (z - 0.5 * delta) — torch's huber_loss
-// forward, operation by operation (a NaN residual fails the compare and stays NaN).  The same
-// grid, strides and tree.
-template <typename TY>
-__global__ __launch_bounds__(kLossThreads) void robust_residual_kernel(
-    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n, double delta,
-    const double* __restrict__ ray_scale, const double* __restrict__ weight,
-    const int32_t* __restrict__ order, double* __restrict__ r_scaled, double* __restrict__ part) {
-    double acc = 0.0;
-    for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
-         j += (int64_t)gridDim.x * kLossThreads) {
-        const int64_t i = order ? (int64_t)order[j] : j;
-        const double r = yhat[i] - (double)y[i];
-        r_scaled[j] = robust_psi(r, delta) * ray_scale[i];
-        const double z = __builtin_fabs(r);
-        double h = z;
-        if (delta > 0.0) h = z < delta ? (0.5 * z) * z : delta * (z - 0.5 * delta);
-        acc += weight[i] * h;
+};
+struct PerRay {
+    const double* __restrict__ ray_scale;
+    const double* __restrict__ weight;
+    bool null() const { return !ray_scale || !weight; }
+};
+struct WsqFid : PerRay {
+    __device__ __forceinline__ double at(double p, double m, int64_t i, double& term) const {
+        const double r = p - m;
+        term = weight[i] * rho_square(r);
+        return r * ray_scale[i];
     }
-    block_partial(acc, part);
-}
+};
+struct RobustFid : PerRay {
+    double delta;
+    __device__ __forceinline__ double at(double p, double m, int64_t i, double& term) const {
+        const double r = p - m;
+        term = weight[i] * (delta > 0.0 ? rho_huber(r, delta) : rho_abs(r));
+        return robust_psi(r, delta) * ray_scale[i];
+    }
+};
+struct PoissonFid : PerRay {
+    double eps;
+    __device__ __forceinline__ double at(double p, double m, int64_t i, double& term) const {
+        const double q = p + eps;
+        term = weight[i] * rho_poisson(p, q, m);
+        return poisson_weight(q, m, ray_scale[i]);
+    }
+};
 
-// The Poisson tail (PoissonLoss: lam * mean(w * (p - y * log(p + eps)))): with p = yhat[i] and
-// q = p + eps (one rounding), r_scaled[j] = ray_scale[i] + ((-ray_scale[i]) * y[i]) / q
-// (poisson_weight, common.hpp: autograd's gradient at p for an incoming ray_scale[i]) and partial
-// sums of weight[i] * (p - y[i] * log(q)) — torch's poisson_nll_loss forward under the mask,
-// operation by operation, the device's log.  No guards: q <= 0 gives NaN or -+inf as in torch.
-// The same grid, strides and tree.
-template <typename TY>
-__global__ __launch_bounds__(kLossThreads) void poisson_residual_kernel(
-    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n, double eps,
-    const double* __restrict__ ray_scale, const double* __restrict__ weight,
+// The residual launch of every fidelity term: for each j, i = order ? order[j] : j (a trace's
+// row -> geometry ray map: r_scaled is then the transposed adjoint's input in trace order,
+// without a separate permutation), p = yhat[i], m = y[i] (float32 or float64, promoted exactly),
+// r_scaled[j] = fid.at(p, m, i, term), and the workgroup's partial sum of the terms.  Every
+// value a single IEEE operation (no contraction); fixed strides and a fixed tree.
+template <typename TY, class FID>
+__global__ __launch_bounds__(kLossThreads) void residual_kernel(
+    const double* __restrict__ yhat, const TY* __restrict__ y, int64_t n, FID fid,
     const int32_t* __restrict__ order, double* __restrict__ r_scaled, double* __restrict__ part) {
 #pragma clang fp contract(off)
     double acc = 0.0;
     for (int64_t j = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; j < n;
          j += (int64_t)gridDim.x * kLossThreads) {
         const int64_t i = order ? (int64_t)order[j] : j;
-        const double p = yhat[i], m = (double)y[i];
-        const double q = p + eps;
-        r_scaled[j] = poisson_weight(q, m, ray_scale[i]);
-        const double t = m * log(q);
-        const double h = p - t;
-        const double wh = weight[i] * h;
-        acc += wh;
+        double term;
+        r_scaled[j] = fid.at(yhat[i], (double)y[i], i, term);
+        acc += term;
     }
     block_partial(acc, part);
 }
@@ -173,7 +177,7 @@ __device__ __forceinline__ double smooth_psi(double r, int kind, double delta) {
     return kind == 0 ? 2.0 * r : robust_psi(r, delta);
 }
 
-// rho(r); HUBER operation by operation as robust_residual_kernel's h.
+// rho(r); HUBER operation by operation as rho_huber.
 __device__ __forceinline__ double smooth_rho(double r, int kind, double delta) {
     if (kind == 0) return r * r;
     const double z = __builtin_fabs(r);
@@ -725,7 +729,7 @@ __global__ __launch_bounds__(kLossThreads) void iso_dual_kernel(
 // The ray side of retrieval.chambolle_pock (include/sphrt_cp.h: the operation order of every
 // kind): p <- prox_{sigma phi*}(p + sigma (2 z_new - z_old)) in place at the thread's own slot
 // i = order[j], its copy in the adjoint's order, and the partial sums of (p+ - p)^2 and of
-// weight * rho(z_new, y) — rho op for op that of the residual kernels above.  48 bytes read and
+// weight * rho(z_new, y) — rho the residual policies' own (rho_square .. rho_poisson).  48 bytes read and
 // 8 or 16 written per ray, coalesced but for the gathers through `order`.  PER_RAY: sigma holds
 // n steps, indexed as ray_scale is (sphrt_dp_ray_dual_f64), instead of one.
 template <typename TY, int KIND, bool PER_RAY>
@@ -750,23 +754,22 @@ __global__ __launch_bounds__(kLossThreads) void cp_ray_dual_kernel(
         double pn, h;
         if constexpr (KIND == SPHRT_CP_SQUARE) {
             pn = t / (1.0 + sg / (2.0 * s));
-            h = r * r;
+            h = rho_square(r);
         } else if constexpr (KIND == SPHRT_CP_ABS) {
             pn = t < -s ? -s : (t > s ? s : t);
-            h = __builtin_fabs(r);
+            h = rho_abs(r);
         } else if constexpr (KIND == SPHRT_CP_HUBER) {
             const double u = t / (1.0 + sg / s), b = s * par;
             pn = u < -b ? -b : (u > b ? b : u);
-            const double z = __builtin_fabs(r);
-            h = z < par ? (0.5 * z) * z : par * (z - 0.5 * par);
+            h = rho_huber(r, par);
         } else {
             const double a1 = fma(sg, par, a);
             const double d = a1 - s, e = a1 + s;
             const double disc = fma((4.0 * sg) * s, m, d * d);
             const double v = 0.5 * (e - sqrt(disc));
             pn = v > s ? s : v;
-            const double lg = m * log(zn + par);
-            h = zn - lg;
+            const double qe = zn + par;
+            h = rho_poisson(zn, qe, m);
         }
         if (s == 0.0) pn = 0.0;
         p[i] = pn;
@@ -839,6 +842,25 @@ static int refuse_cg(const char* me, int64_t n, int64_t n_part, bool check_part)
     return 0;
 }
 
+// The host side of the four residual entries: the refusals in their order (`me`: the entry's
+// name), the stream's device, residual_kernel for y's type, and the launch check under `label`.
+template <class FID>
+static int residual_launch(const char* me, const char* label, FID fid, const double* yhat,
+                           const void* y, int y_is_f64, int64_t n, const int32_t* order,
+                           double* r_scaled, double* partial_sums, void* stream) {
+    if (n <= 0) return fail("%s: empty measurement", me);
+    if (!yhat || !y || fid.null() || !r_scaled || !partial_sums) return fail("null buffer");
+    StreamGuard guard(stream);
+    const dim3 grid(loss_grid(n)), block(kLossThreads);
+    if (y_is_f64)
+        hipLaunchKernelGGL((residual_kernel<double, FID>), grid, block, 0, (hipStream_t)stream,
+                           yhat, (const double*)y, n, fid, order, r_scaled, partial_sums);
+    else
+        hipLaunchKernelGGL((residual_kernel<float, FID>), grid, block, 0, (hipStream_t)stream,
+                           yhat, (const float*)y, n, fid, order, r_scaled, partial_sums);
+    return check_launch(label);
+}
+
 }  // namespace sphrt
 
 using namespace sphrt;
@@ -848,37 +870,16 @@ extern "C" int64_t sphrt_loss_partials(int64_t n) { return n > 0 ? (int64_t)loss
 extern "C" int sphrt_sq_residual_f64(const double* yhat, const void* y, int y_is_f64, int64_t n,
                                      double scale, const int32_t* order, double* r_scaled,
                                      double* partial_sums, void* stream) {
-    if (n <= 0) return fail("sphrt_sq_residual_f64: empty measurement");
-    if (!yhat || !y || !r_scaled || !partial_sums) return fail("null buffer");
-    StreamGuard guard(stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (y_is_f64)
-        hipLaunchKernelGGL(sq_residual_kernel<double>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                           st, yhat, (const double*)y, n, scale, order, r_scaled, partial_sums);
-    else
-        hipLaunchKernelGGL(sq_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                           st, yhat, (const float*)y, n, scale, order, r_scaled, partial_sums);
-    return check_launch("sq_residual");
+    return residual_launch("sphrt_sq_residual_f64", "sq_residual", SqFid{scale}, yhat, y, y_is_f64,
+                           n, order, r_scaled, partial_sums, stream);
 }
 
 extern "C" int sphrt_wsq_residual_f64(const double* yhat, const void* y, int y_is_f64, int64_t n,
                                       const double* ray_scale, const double* weight,
                                       const int32_t* order, double* r_scaled,
                                       double* partial_sums, void* stream) {
-    if (n <= 0) return fail("sphrt_wsq_residual_f64: empty measurement");
-    if (!yhat || !y || !ray_scale || !weight || !r_scaled || !partial_sums)
-        return fail("null buffer");
-    StreamGuard guard(stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (y_is_f64)
-        hipLaunchKernelGGL(wsq_residual_kernel<double>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                           st, yhat, (const double*)y, n, ray_scale, weight, order, r_scaled,
-                           partial_sums);
-    else
-        hipLaunchKernelGGL(wsq_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads), 0,
-                           st, yhat, (const float*)y, n, ray_scale, weight, order, r_scaled,
-                           partial_sums);
-    return check_launch("wsq_residual");
+    return residual_launch("sphrt_wsq_residual_f64", "wsq_residual", WsqFid{{ray_scale, weight}},
+                           yhat, y, y_is_f64, n, order, r_scaled, partial_sums, stream);
 }
 
 extern "C" int sphrt_robust_residual_f64(const double* yhat, const void* y, int y_is_f64,
@@ -888,20 +889,9 @@ extern "C" int sphrt_robust_residual_f64(const double* yhat, const void* y, int 
                                          double* partial_sums, void* stream) {
     double rd;
     if (int e = refuse_robust(kind, delta, rd)) return e;
-    if (n <= 0) return fail("sphrt_robust_residual_f64: empty measurement");
-    if (!yhat || !y || !ray_scale || !weight || !r_scaled || !partial_sums)
-        return fail("null buffer");
-    StreamGuard guard(stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (y_is_f64)
-        hipLaunchKernelGGL(robust_residual_kernel<double>, dim3(loss_grid(n)), dim3(kLossThreads),
-                           0, st, yhat, (const double*)y, n, rd, ray_scale, weight, order,
-                           r_scaled, partial_sums);
-    else
-        hipLaunchKernelGGL(robust_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads),
-                           0, st, yhat, (const float*)y, n, rd, ray_scale, weight, order, r_scaled,
-                           partial_sums);
-    return check_launch("robust_residual");
+    return residual_launch("sphrt_robust_residual_f64", "robust_residual",
+                           RobustFid{{ray_scale, weight}, rd}, yhat, y, y_is_f64, n, order,
+                           r_scaled, partial_sums, stream);
 }
 
 extern "C" int sphrt_poisson_residual_f64(const double* yhat, const void* y, int y_is_f64,
@@ -909,20 +899,9 @@ extern "C" int sphrt_poisson_residual_f64(const double* yhat, const void* y, int
                                           const double* weight, const int32_t* order,
                                           double* r_scaled, double* partial_sums, void* stream) {
     if (int e = refuse_poisson(eps)) return e;
-    if (n <= 0) return fail("sphrt_poisson_residual_f64: empty measurement");
-    if (!yhat || !y || !ray_scale || !weight || !r_scaled || !partial_sums)
-        return fail("null buffer");
-    StreamGuard guard(stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (y_is_f64)
-        hipLaunchKernelGGL(poisson_residual_kernel<double>, dim3(loss_grid(n)), dim3(kLossThreads),
-                           0, st, yhat, (const double*)y, n, eps, ray_scale, weight, order,
-                           r_scaled, partial_sums);
-    else
-        hipLaunchKernelGGL(poisson_residual_kernel<float>, dim3(loss_grid(n)), dim3(kLossThreads),
-                           0, st, yhat, (const float*)y, n, eps, ray_scale, weight, order, r_scaled,
-                           partial_sums);
-    return check_launch("poisson_residual");
+    return residual_launch("sphrt_poisson_residual_f64", "poisson_residual",
+                           PoissonFid{{ray_scale, weight}, eps}, yhat, y, y_is_f64, n, order,
+                           r_scaled, partial_sums, stream);
 }
 
 extern "C" int sphrt_neg_reg_f64(const double* d, int64_t n, double c_neg, double* g,

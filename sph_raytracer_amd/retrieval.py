@@ -11,6 +11,7 @@ launches per iteration, three csrc/loss.hip launches for the vector side, no lea
 """
 import ctypes
 import math
+import types
 
 import torch as t
 
@@ -228,6 +229,124 @@ def _loop_terms(f, y, model, coeffs, loss_fns, optim_vars):
     return sq, neg, smooth
 
 
+def _stored_loop_setup(f, yd, w_res, s_res, stage=True):
+    """What a direct loop over a stored Operator arranges once: the loop's forward descriptor (or
+    None: f(d) itself), the adjoint's input order, the measurements and the per-ray factors
+    (None: unweighted) in the order the loop's forward writes — trace positions when the
+    descriptor's rows can be pointed at them, else geometry rays, and then `res_order` gathers
+    the adjoint's input (the same values in the same order either way: bitwise the same
+    iterates).  `stage`: take the brick-staged descriptor where there is one (its forward packs d
+    itself unless the caller keeps the stage current: `_gd_direct`'s Adam launch); without it
+    only the plain copy of the trace's descriptor, which a reordered trace needs.
+    -> (loop_desc, order, res_order, y_res, w_res, s_res, keep): keep = (the staged pair, the
+    trace-position lists), either None when not in use, for the caller to hold."""
+    f64, n_meas = t.float64, yd.numel()
+    staged = f._stage_for_loop(f64) if stage else None
+    if staged is not None and f._csr['n'] != n_meas:
+        staged = None
+    order = f._adjoint_trace_order()
+    if order is not None and order.numel() != n_meas:
+        order = None
+    loop_desc = staged[0] if staged is not None else None
+    y_res, res_order, keep_rows = yd.reshape(-1), order, None
+    if order is not None:
+        sd = loop_desc if loop_desc is not None else f._loop_descriptor(f64)
+        keep_rows = f._trace_position_rows(sd) if sd is not None else None
+        if keep_rows is not None:
+            loop_desc = sd
+            y_res, res_order = y_res.index_select(0, f._ray_id_long()), None
+            if w_res is not None:
+                w_res, s_res = (v.index_select(0, f._ray_id_long())
+                                for v in (w_res, s_res))
+    return loop_desc, order, res_order, y_res, w_res, s_res, (staged, keep_rows)
+
+
+def _fidelity_stage(f, y, fid, gradient=True, n_total=None, stage=True, zero_m=False):
+    """The fidelity side of a direct loop over `f`, arranged once per solve; `_gd_direct`,
+    `_normal_direct` and `_chambolle_pock_direct` all read it.
+
+        yd, n_meas, y_f64   the measurements as measured (detached, contiguous; a float32 y is
+                            promoted inside the kernels, exactly), their count, the float64 flag
+        n_norm, c           the mean's N (`n_total`: the whole stack's, distributed.gd) and lam / N
+        robust, poisson     `_robust_of`, `_poisson_of` of the term
+        w_res, s_res        the loss's weights w and the per-ray factors s, flat float64, in the
+                            order y_res is in.  `gradient`: s is the factor of the gradient's
+                            residual — for the square term (c * w) * 2, and None (as w) for a unit
+                            mask, where the scalar `scale` = 2 c serves; for a robust or Poisson
+                            term c * w, always arrays (a unit mask: ones, and a fill of c).
+                            Without it (chambolle_pock's ray dual): c * w for every term, always
+                            arrays.
+        loop_desc, order, res_order, y_res, staged, positions
+                            over a stored Operator, `_stored_loop_setup` (`stage` is its flag);
+                            positions: the loop's forward writes trace positions
+        m64, weighted, fixed   over a MatrixFreeOperator: float64 measurements and the masked
+                            square term's (s, max|s| or None) for the fused trace (`gradient`
+                            only), the deterministic operator's (`_fixed_buffers`,) or ()
+        residual(yhat, r_scaled, part, stream, against_y=True)
+                            the term's csrc/loss.hip launch, bound once (`gradient` only): the
+                            adjoint's input of the forward `yhat` into r_scaled — through
+                            res_order where the adjoint takes trace order: no permutation launch —
+                            and the loss's partial sums into part; against_y=False: against
+                            `zero_m`, float64 zeros held when the caller asks for them"""
+    from . import _lib
+    from .raytracer import MatrixFreeOperator, _scale_max
+    lib = _lib.load()
+    dev, f64 = f._cdev, t.float64
+    st = types.SimpleNamespace(fused=isinstance(f, MatrixFreeOperator))
+    st.yd = yd = y.detach().contiguous()
+    st.n_meas = n_meas = yd.numel()
+    st.y_f64 = int(yd.dtype == f64)
+    st.n_norm = n_meas if n_total is None else n_total
+    st.c = c = fid.lam / st.n_norm
+    st.scale = 2 * c
+    st.robust, st.poisson = _robust_of(fid), _poisson_of(fid)
+    square = gradient and st.robust is None and st.poisson is None
+    w = s = None
+    if isinstance(fid.projection_mask, t.Tensor):
+        w = fid.projection_mask.detach().to(f64).expand(yd.shape).contiguous().reshape(-1)
+        s = (c * w) * 2 if square else c * w
+    elif not square:
+        w = t.ones(n_meas, dtype=f64, device=dev)
+        s = t.full((n_meas,), c, dtype=f64, device=dev)
+    st.loop_desc = st.order = st.res_order = st.staged = None
+    st.y_res, st.positions = yd.reshape(-1), False
+    st.m64 = st.weighted = None
+    st.fixed = ()
+    st.zero_m = t.zeros(n_meas, dtype=f64, device=dev) if zero_m else None
+    if not st.fused:
+        st.loop_desc, st.order, st.res_order, st.y_res, w, s, keep = _stored_loop_setup(
+            f, yd, w, s, stage=stage)
+        st.staged, st.positions, st._keep = keep[0], keep[1] is not None, keep
+    elif gradient:
+        # the fused trace subtracts float64 measurements; a deterministic operator's fixed-point
+        # bound on the masked square term: max|s|, read back once for the loop
+        st.m64 = yd.to(f64).reshape(-1)
+        if square and s is not None:
+            st.weighted = (s, _scale_max(s) if f.deterministic else None)
+    if st.fused and f.deterministic:
+        # (the integer accumulator and scale record, once for the whole loop)
+        st.fixed = (f._fixed_buffers(),)
+    st.w_res, st.s_res = w, s
+    if not gradient:
+        return st
+    if st.poisson is not None:
+        name, par = 'sphrt_poisson_residual_f64', (st.poisson,)
+    elif st.robust is not None:
+        name, par = 'sphrt_robust_residual_f64', st.robust
+    else:
+        name, par = 'sphrt_sq_residual_f64' if s is None else 'sphrt_wsq_residual_f64', ()
+    entry = getattr(lib, name)
+    factors = (*par, _lib.ptr(s), _lib.ptr(w)) if s is not None else (st.scale,)
+    against = {True: (_lib.ptr(st.y_res), st.y_f64), False: (_lib.ptr(st.zero_m), 1)}
+    order = _lib.ptr(st.res_order)
+
+    def residual(yhat, r_scaled, part, stream, against_y=True):
+        _lib.check(entry(_lib.ptr(yhat), *against[against_y], n_meas, *factors, order,
+                         _lib.ptr(r_scaled), _lib.ptr(part), stream), name)
+    st.residual = residual
+    return st
+
+
 def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, reduce=None,
                n_total=None):
     """`gd` for `_direct_plan` loops: the same arithmetic as autograd's, op by op, so the
@@ -281,78 +400,24 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
     before the regulariser and the optimiser step (which are then identical on every rank) and
     to the SquareLoss sums after the loop."""
     from . import _lib
-    from .raytracer import MatrixFreeOperator
-    fused = isinstance(f, MatrixFreeOperator)
     sq, neg = plan[:2]
     smooth = plan[2] if len(plan) > 2 else None
     losses = {fn: [] for fn in loss_fns}
     y.requires_grad_()                 # (the reference's own side effect on y)
-    # y as measured: a float32 y is promoted inside the residual kernel (exactly, as y - f(d)
-    # promotes it); anything else is converted to float64 once
-    yd = y.detach()
-    if yd.dtype not in (t.float32, t.float64):
-        yd = yd.to(coeffs.dtype)
-    yd = yd.contiguous()
-    n_norm = yd.numel() if n_total is None else n_total     # the SquareLoss mean's N
-    c_sq = sq.lam / n_norm
-    c_neg = neg.lam / coeffs.numel() if neg is not None else 0.0
     step = _split_adam(opt, coeffs)
-    bar = _Bar(range(num_iterations), progress_bar)
-    lib = _lib.load()
-    n_meas, n_vox = yd.numel(), coeffs.numel()
-    # Adam keeps the forward's brick-staged density current (no pack launch per iteration)
-    staged = f._stage_for_loop(coeffs.dtype) if step is not None and not fused else None
-    if staged is not None and f._csr['n'] != n_meas:
-        staged = None
-    order = f._adjoint_trace_order() if not fused else None
-    if order is not None and order.numel() != n_meas:
-        order = None
-    # the loop's own forward descriptor (a copy of the trace's): the staged one above, and with a
-    # reordered trace — whose adjoint takes its input in trace order — one that writes f(d) in
-    # that order too; the measurements are then permuted once and the residual kernel streams
-    # both (the same values in the same order: bitwise the same iterates)
-    loop_desc = staged[0] if staged is not None else None
-    y_res, res_order, keep_rows = yd, order, None
-    if order is not None:
-        sd = loop_desc if loop_desc is not None else f._loop_descriptor(coeffs.dtype)
-        keep_rows = f._trace_position_rows(sd) if sd is not None else None
-        if keep_rows is not None:
-            loop_desc = sd
-            y_res, res_order = yd.reshape(-1).index_select(0, f._ray_id_long()), None
-    yhat_buf = t.empty(n_meas, dtype=coeffs.dtype, device=coeffs.device) \
-        if loop_desc is not None or fused else None
-    # a projection_mask: the loss's weights w and the residual's factors s, once, laid out as the
-    # residual kernel reads y (in trace order where y was permuted above)
-    w_res = s_res = weighted = None
-    robust, poisson = _robust_of(sq), _poisson_of(sq)
+    # the fidelity side; over a stored Operator the brick-staged forward only with the Adam
+    # launch, which keeps the stage current (no pack launch per iteration)
+    fs = _fidelity_stage(f, y, sq, n_total=n_total, stage=step is not None)
+    fused, yd, n_norm, staged, loop_desc = fs.fused, fs.yd, fs.n_norm, fs.staged, fs.loop_desc
+    m64, s_res, fixed, robust, poisson = fs.m64, fs.s_res, fs.fixed, fs.robust, fs.poisson
     # (a deterministic Poisson loop: two traces, the stored loop's order of launches)
     two_trace = poisson is not None and fused and bool(f.deterministic)
-    if robust is not None or poisson is not None:
-        # a robust or Poisson term's factors are always arrays (a unit mask: ones, and lam / N
-        # itself)
-        if isinstance(sq.projection_mask, t.Tensor):
-            w_res = sq.projection_mask.detach().to(t.float64).expand(yd.shape).contiguous() \
-                .reshape(-1)
-            s_res = c_sq * w_res
-        else:
-            w_res = t.ones(n_meas, dtype=t.float64, device=coeffs.device)
-            s_res = t.full((n_meas,), c_sq, dtype=t.float64, device=coeffs.device)
-        if keep_rows is not None:
-            w_res, s_res = (v.index_select(0, f._ray_id_long()) for v in (w_res, s_res))
-    elif isinstance(sq.projection_mask, t.Tensor):
-        w_res = sq.projection_mask.detach().to(t.float64).expand(yd.shape).contiguous().reshape(-1)
-        s_res = (c_sq * w_res) * 2
-        if keep_rows is not None:
-            w_res, s_res = (v.index_select(0, f._ray_id_long()) for v in (w_res, s_res))
-        if fused:
-            # (a deterministic operator's fixed-point bound: max|s|, read back once for the loop)
-            from .raytracer import _scale_max
-            weighted = (s_res, _scale_max(s_res) if f.deterministic else None)
-    # the fused trace subtracts float64 measurements (a float32 y promoted once, exactly)
-    m64 = yd.to(t.float64).reshape(-1) if fused else None
-    # a deterministic operator's integer accumulator and scale record, once for the whole loop
-    # (every iteration: scale, the fixed-point trace, finalize into g — nothing allocated)
-    fixed = (f._fixed_buffers(),) if fused and f.deterministic else ()
+    c_neg = neg.lam / coeffs.numel() if neg is not None else 0.0
+    bar = _Bar(range(num_iterations), progress_bar)
+    lib = _lib.load()
+    n_meas, n_vox = fs.n_meas, coeffs.numel()
+    yhat_buf = t.empty(n_meas, dtype=coeffs.dtype, device=coeffs.device) \
+        if loop_desc is not None or fused else None
     # every iteration's loss as the workgroup partial sums of its fused kernel, one row per
     # iteration, summed once after the loop (no reduction launch, no host sync per iteration)
     ps, pn = lib.sphrt_loss_partials(n_meas), lib.sphrt_loss_partials(n_vox)
@@ -393,10 +458,11 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                         # (s does not change: the record is written by the first iteration)
                         f._robust_into(d, m64, s_res, robust, yhat_buf, g, *fixed,
                                        scaled=bool(fixed) and it > 0)
-                    elif weighted is None:
-                        f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed)
+                    elif fs.weighted is None:
+                        f._normal_into(d, m64, fs.scale, yhat_buf, g, *fixed)
                     else:
-                        f._normal_into(d, m64, 2 * c_sq, yhat_buf, g, *fixed, weighted=weighted)
+                        f._normal_into(d, m64, fs.scale, yhat_buf, g, *fixed,
+                                       weighted=fs.weighted)
                     yhat = yhat_buf.view(yd.shape)
                 elif loop_desc is not None:
                     # (staged: the forward reads the brick copy the previous Adam launch wrote;
@@ -410,39 +476,13 @@ def _gd_direct(f, y, coeffs, loss_fns, opt, plan, num_iterations, progress_bar, 
                 if yhat.shape != yd.shape:
                     raise ValueError(f'measurements {tuple(yd.shape)} do not match the operator '
                                      f'output {tuple(yhat.shape)}')
-                # r = f(d) - y, r * (2 lam / N) (the adjoint's input) and the partial sums of
-                # r * r (the loss) in one launch (csrc/loss.hip)
-                # (in the trace's ray order when the adjoint takes that: no permutation launch)
+                # the adjoint's input and the partial sums of the loss in one launch
+                # (csrc/loss.hip; the docstring's s and sums, by the fidelity term)
                 r_scaled = t.empty_like(yhat)
-                if poisson is not None:
-                    # (r_scaled = s_i + ((-s_i) y) / (f(d) + eps), and the partial sums of
-                    # w_i * (f(d) - y * log(f(d) + eps)))
-                    _lib.check(lib.sphrt_poisson_residual_f64(
-                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
-                        poisson, _lib.ptr(s_res), _lib.ptr(w_res), _lib.ptr(res_order),
-                        _lib.ptr(r_scaled), _lib.ptr(part_sq[it]), stream),
-                        'sphrt_poisson_residual_f64')
-                elif robust is not None:
-                    # (r_scaled = psi(r) * s_i, and the partial sums of w_i * |r| or w_i * huber(r))
-                    _lib.check(lib.sphrt_robust_residual_f64(
-                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
-                        robust[0], robust[1], _lib.ptr(s_res), _lib.ptr(w_res),
-                        _lib.ptr(res_order), _lib.ptr(r_scaled), _lib.ptr(part_sq[it]), stream),
-                        'sphrt_robust_residual_f64')
-                elif w_res is None:
-                    _lib.check(lib.sphrt_sq_residual_f64(
-                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
-                        2 * c_sq, _lib.ptr(res_order), _lib.ptr(r_scaled), _lib.ptr(part_sq[it]),
-                        stream), 'sphrt_sq_residual_f64')
-                else:
-                    # (with a projection_mask: r * s_i, and the partial sums of w_i * (r * r))
-                    _lib.check(lib.sphrt_wsq_residual_f64(
-                        _lib.ptr(yhat), _lib.ptr(y_res), int(yd.dtype == t.float64), n_meas,
-                        _lib.ptr(s_res), _lib.ptr(w_res), _lib.ptr(res_order), _lib.ptr(r_scaled),
-                        _lib.ptr(part_sq[it]), stream), 'sphrt_wsq_residual_f64')
+                fs.residual(yhat, r_scaled, part_sq[it], stream)
                 if not fused:
                     g = f._apply_adjoint(r_scaled, tuple(d.shape), d.dtype, d.device,
-                                         trace_order=order is not None)
+                                         trace_order=fs.order is not None)
                 elif two_trace:
                     g = t.empty_like(d)
                     f._backproject_fixed_into(r_scaled, g, fixed[0])
@@ -763,35 +803,6 @@ def _kernel_sum(part):
     return ((((0.0 + v[:, 0]) + v[:, 1]) + v[:, 2]) + v[:, 3]).reshape(part.shape[:-1])
 
 
-def _stored_loop_setup(f, yd, w_res, s_res):
-    """What a direct loop over a stored Operator arranges once, as _gd_direct does: the loop's
-    forward descriptor (or None: f(d) itself), the adjoint's input order, the measurements and
-    the per-ray factors (None: unweighted) in the order the loop's forward writes — trace
-    positions when the descriptor's rows can be pointed at them, else geometry rays, and then
-    `res_order` gathers the adjoint's input.  (The brick-staged forward packs d itself.)
-    -> (loop_desc, order, res_order, y_res, w_res, s_res, keep): keep = (the staged pair, the
-    trace-position lists), either None when not in use, for the caller to hold."""
-    f64, n_meas = t.float64, yd.numel()
-    staged = f._stage_for_loop(f64)
-    if staged is not None and f._csr['n'] != n_meas:
-        staged = None
-    order = f._adjoint_trace_order()
-    if order is not None and order.numel() != n_meas:
-        order = None
-    loop_desc = staged[0] if staged is not None else None
-    y_res, res_order, keep_rows = yd.reshape(-1), order, None
-    if order is not None:
-        sd = loop_desc if loop_desc is not None else f._loop_descriptor(f64)
-        keep_rows = f._trace_position_rows(sd) if sd is not None else None
-        if keep_rows is not None:
-            loop_desc = sd
-            y_res, res_order = y_res.index_select(0, f._ray_id_long()), None
-            if w_res is not None:
-                w_res, s_res = (v.index_select(0, f._ray_id_long())
-                                for v in (w_res, s_res))
-    return loop_desc, order, res_order, y_res, w_res, s_res, (staged, keep_rows)
-
-
 def _normal_direct(f, y, sq, smooth, x):
     """apply(d) / apply(d, against_y=True) = A^T(s (A d - m)) + G d, m = 0 or y, on the operator's
     own entries (`_cg_is_direct`), for contiguous float64 volumes like `x` on the operator's GPU:
@@ -801,62 +812,37 @@ def _normal_direct(f, y, sq, smooth, x):
     then, with a smooth term, one sphrt_smooth_reg_f64 launch.  The result is a buffer the next
     application may overwrite.  -> (apply, the count of partial sums of a launch over a volume)."""
     from . import _lib
-    from .raytracer import MatrixFreeOperator, _scale_max
     lib = _lib.load()
-    fused = isinstance(f, MatrixFreeOperator)
     dev, f64 = f._cdev, t.float64
-    yd = y.detach().contiguous()
-    y_f64 = int(yd.dtype == f64)
-    n_meas, n_vox = yd.numel(), x.numel()
-    c_sq = sq.lam / n_meas
-    w_res = s_res = None
-    if isinstance(sq.projection_mask, t.Tensor):     # as _gd_direct forms them
-        w_res = sq.projection_mask.detach().to(f64).expand(yd.shape).contiguous().reshape(-1)
-        s_res = (c_sq * w_res) * 2
+    fs = _fidelity_stage(f, y, sq, zero_m=True)
+    n_meas, n_vox = fs.n_meas, x.numel()
     pn, ps = lib.sphrt_loss_partials(n_vox), lib.sphrt_loss_partials(n_meas)
     part_tmp = t.empty(max(pn, ps), dtype=f64, device=dev)   # (sums nobody reads)
     wrap = smooth.wraps(f) if smooth is not None else None
     q_buf = t.empty(n_meas, dtype=f64, device=dev)
-    zero_m = t.zeros(n_meas, dtype=f64, device=dev)
-    if fused:
-        m64 = yd.to(f64).reshape(-1)
-        weighted = None if s_res is None else \
-            (s_res, _scale_max(s_res) if f.deterministic else None)
-        fixed = (f._fixed_buffers(),) if f.deterministic else ()
+    if fs.fused:
         h_buf = t.empty_like(x)
 
         def normal(d, against_y):
             """A^T(s (A d - m)), m = y or 0, into h_buf from one trace."""
-            if not fixed:
+            if not fs.fixed:
                 h_buf.zero_()
-            f._normal_into(d, m64 if against_y else zero_m, 2 * c_sq, q_buf, h_buf, *fixed,
-                           weighted=weighted)
+            f._normal_into(d, fs.m64 if against_y else fs.zero_m, fs.scale, q_buf, h_buf,
+                           *fs.fixed, weighted=fs.weighted)
             return h_buf
     else:
-        loop_desc, order, res_order, y_res, w_res, s_res, _keep = _stored_loop_setup(
-            f, yd, w_res, s_res)
         rs_buf = t.empty(n_meas, dtype=f64, device=dev)
 
         def normal(d, against_y):
             """A^T(s (A d - m)), m = y or 0: forward, scaled residual, adjoint."""
-            stream = _lib.stream_of(dev)
-            if loop_desc is not None:
-                f._forward_staged(d, q_buf, loop_desc)
+            if fs.loop_desc is not None:
+                f._forward_staged(d, q_buf, fs.loop_desc)
                 q = q_buf
             else:
                 q = f(d).reshape(-1)
-            m, m_f64 = (y_res, y_f64) if against_y else (zero_m, 1)
-            if w_res is None:
-                _lib.check(lib.sphrt_sq_residual_f64(
-                    _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, 2 * c_sq, _lib.ptr(res_order),
-                    _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream), 'sphrt_sq_residual_f64')
-            else:
-                _lib.check(lib.sphrt_wsq_residual_f64(
-                    _lib.ptr(q), _lib.ptr(m), m_f64, n_meas, _lib.ptr(s_res), _lib.ptr(w_res),
-                    _lib.ptr(res_order), _lib.ptr(rs_buf), _lib.ptr(part_tmp), stream),
-                    'sphrt_wsq_residual_f64')
-            return f._apply_adjoint(rs_buf.view(yd.shape), tuple(d.shape), d.dtype, dev,
-                                    trace_order=order is not None)
+            fs.residual(q, rs_buf, part_tmp, _lib.stream_of(dev), against_y)
+            return f._apply_adjoint(rs_buf.view(fs.yd.shape), tuple(d.shape), d.dtype, dev,
+                                    trace_order=fs.order is not None)
 
     def apply(d, against_y=False):
         h = normal(d, against_y)
@@ -1643,7 +1629,8 @@ def chambolle_pock(f, y, loss_fns, x0=None, num_iterations=100, damp=0.0, lower=
 
 
 def _cp_terms(y, loss_fns, damp, num_iterations, who):
-    """(the fidelity term, the TV term or None) of a total `chambolle_pock` solves; ValueError naming what it does not, worded as `_cg_terms` words it."""
+    """(the fidelity term, the TV term or None) of a total `chambolle_pock` solves; ValueError
+    naming what it does not, worded as `_cg_terms` words it."""
     if not isinstance(y, t.Tensor):
         raise ValueError(f'{who} needs measurements y as a tensor, not {type(y).__name__}')
     if not _number(damp) or not 0 <= damp < float('inf'):
@@ -1872,7 +1859,7 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
     `_forward_into`: a second trace) and sphrt_cp_ray_dual_f64 (include/sphrt_cp.h: the ray
     dual's prox in place, its copy in the adjoint's order, partial sums of its change and of the
     fidelity).  Measurements, weights and the ray order over an Operator are arranged as
-    `_normal_direct` arranges them (`_stored_loop_setup`); p lives in the order the loop's
+    `_normal_direct` arranges them (`_fidelity_stage`); p lives in the order the loop's
     forward writes and info['ray_dual'] is put back into geometry order at the end.  tau and
     sigma are one-element device tensors the launches read through pointers — L_A comes from the
     power method in torch over `_normal_direct`'s application of A^T A — so nothing is read back
@@ -1903,16 +1890,13 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
         n_vox = x.numel()
         with_tv = tv.term is not None
         c = 2 * damp / n_vox
-        yd = y.detach().contiguous()
-        n_meas = yd.numel()
         kind, par = _cp_kind(fid)
-        s_bar = fid.lam / n_meas
-        if isinstance(fid.projection_mask, t.Tensor):
-            w_ray = fid.projection_mask.detach().to(f64).expand(yd.shape).contiguous().reshape(-1)
-            s_ray = s_bar * w_ray
-        else:
-            w_ray = t.ones(n_meas, dtype=f64, device=dev)
-            s_ray = t.full((n_meas,), s_bar, dtype=f64, device=dev)
+        # (the ray dual's factors: s = s_bar w, arrays for every term; p lives in y_ray's order)
+        fs = _fidelity_stage(f, y, fid, gradient=False)
+        yd, n_meas, s_bar, y_f64 = fs.yd, fs.n_meas, fs.c, fs.y_f64
+        y_ray, w_ray, s_ray = fs.y_res, fs.w_res, fs.s_res
+        order, res_order, loop_desc, positions = fs.order, fs.res_order, fs.loop_desc, fs.positions
+        fixed = fs.fixed[0] if fs.fixed else None
         if diagonal:
             pn = lib.sphrt_loss_partials(n_vox)
             LA = t.zeros(1, dtype=f64, device=dev)
@@ -1925,16 +1909,7 @@ def _chambolle_pock_direct(f, y, fid, tv, x0, num_iterations, damp, lower, upper
             tau, sigma = _cp_steps(LA, tv.bound, s_bar, c, dual_ratio)
             sigma_tv = sigma
         ps = lib.sphrt_loss_partials(n_meas)
-        y_ray, order, res_order, loop_desc, positions, keep = yd.reshape(-1), None, None, None, \
-            False, None
-        if fused:
-            fixed = f._fixed_buffers() if f.deterministic else None
-            g_buf = t.empty_like(x)
-        else:
-            loop_desc, order, res_order, y_ray, w_ray, s_ray, keep = _stored_loop_setup(
-                f, yd, w_ray, s_ray)
-            positions = keep[1] is not None
-        y_f64 = int(y_ray.dtype == f64)
+        g_buf = t.empty_like(x) if fused else None
         z, z_new = (t.empty(n_meas, dtype=f64, device=dev) for _ in range(2))
         p = t.zeros(n_meas, dtype=f64, device=dev)
         p_adj = t.zeros(n_meas, dtype=f64, device=dev) if res_order is not None else None

@@ -214,6 +214,26 @@ def test_float32_measurements(name, kind, gpu, monkeypatch):
     assert cc.rel_err(x.cpu().numpy(), want) <= cc.SOLVE_TOL
 
 
+@pytest.mark.parametrize('y32', [False, True])
+@pytest.mark.parametrize('masked', [False, True])
+def test_direct_gradient_is_autograd_s_bitwise(masked, y32, gpu):
+    """Over the stored Operator, `_normal_direct`'s application against y — the loop's forward,
+    the fidelity stage's residual launch, the adjoint: what cg, fista, primal_dual and
+    chambolle_pock's power method start from — has the bits of autograd's gradient of
+    lam * mean(w * (y - f(x))^2) through the loss class, at an x with entries of both signs: the
+    equality `_gd_direct` documents, for a unit and a tensor mask, a float64 and a float32 y."""
+    from sph_raytracer_amd import retrieval
+    grid, _, op, y, _ = _problem('tiny', gpu)
+    y = y.float() if y32 else y
+    sq, = _terms('tiny', gpu, masked, None)
+    g = tr.Generator().manual_seed(5)
+    x = (tr.rand(tuple(grid.shape), dtype=F64, generator=g) - 0.25).to(gpu)
+    want = cc.grad_total(op, y, [sq], 0.0, x)
+    with tr.no_grad(), tr.cuda.device(gpu):
+        got = retrieval._normal_direct(op, y, sq, None, x)[0](x, against_y=True)
+    assert bool(want.any()) and np.array_equal(_bits(got), _bits(want))
+
+
 def test_inputs_that_take_the_generic_path_still_solve(gpu, monkeypatch):
     """A non-contiguous x0, a float32 x0, and a dynamic operator (view i <-> time slice i)."""
     from sph_raytracer_amd import Operator, SphericalGrid
